@@ -16,7 +16,12 @@ same for every N.
     python bench.py [--gpus N --steps K --warmup W] [--n-seqs 100000 --seq-len 400]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     python bench.py --workload family|realmix [--order sorted|input]     ragged lengths (below)
-    python bench.py --pmc off                                            without the two profiled passes behind roofline.traffic (below)
+    python bench.py --full [--pmc off] [--no-parity] [--no-cpu-baseline] also everything that is not the headline figure (below)
+    python bench.py --dump-outputs DIR                                   what the last timed step returned, as DIR/<name>.npy
+
+A plain run sets up, warms up, times its --steps steps, writes --dump-outputs if asked and prints the line.  `parity`,
+`cpu_baseline` and `roofline.traffic` (below) take runs of their own and belong to `--full`; without it the line has
+`parity.sampled_pairs` = 0, no `cpu_baseline` and `roofline.traffic` = null.
 
 Workloads.  The default (`uniform`: BASELINE.json's configs[3], 100 000 x 400 aa) and its line are what they always
 were.  `--workload family` (one ancestor of --seq-len 300 residues, 25 % substitutions, lengths uniform in [0.7 L, L]:
@@ -26,11 +31,11 @@ descending: what every tree generator uploads) or `--order input` as read (what 
 has the same fields; cells, algorithmic bytes and VALU operations are summed over the actual lengths
 (sum over pairs of len_partner x ceil(len_ref / 32) x 3 lane-ops), `config.workload` names the set and the order.
 
-`roofline.traffic` (one rank): after the timed loop this command is run again twice under `rocprofv3 --kernel-trace --pmc
+`roofline.traffic` (`--full`, one rank): after the timed loop this command is run again twice under `rocprofv3 --kernel-trace --pmc
 FETCH_SIZE` resp. `WRITE_SIZE` (one step each, separate passes as MI355X_MICROARCH.md prescribes; ~15 s each), and
 `roofline.traffic` = (2 x FETCH_SIZE + WRITE_SIZE) x 1024 summed over the LCS kernels of the step (gfx950: FETCH_SIZE counts
-half of a wide streaming read).  By default whenever rocprofv3 is on PATH (`--pmc auto`); with `--pmc off`, with more than one
-rank, or without rocprofv3 `traffic` is null -- it is never imported from a file.
+half of a wide streaming read).  With `--full` whenever rocprofv3 is on PATH (`--pmc auto`); without `--full`, with `--pmc off`,
+with more than one rank, or without rocprofv3 `traffic` is null -- it is never imported from a file.
 
 Both forms work for N > 1: started plainly (no WORLD_SIZE in the environment), `bench.py --gpus N` starts its
 N ranks itself (one process per GPU, LOCAL_RANK binding, rendezvous on 127.0.0.1) and relays rank 0's line.
@@ -41,9 +46,9 @@ or RCCL error ends the run with the rank, the transport and the error text inste
 library's own multi-GPU path behind `famsa-gpu -gpu a,b,..` (key exchange: grouped ncclAllGather when every
 context has its own device, else peer copies).
 
-Rank 0 prints ONE JSON line.  After the timed region a sample of the triangle the last step left
-in HBM is compared with the oracle (oracle/lcs_oracle.c) -- `parity`.  `cpu_baseline` times the
-REFERENCE's own AVX2 path (oracle/_ref/libfamsa_ref.so = /root/reference sources +
+Rank 0 prints ONE JSON line.  With `--full`, after the timed region a sample of the triangle the last step
+left in HBM is compared with the oracle (oracle/lcs_oracle.c) -- `parity` -- and `cpu_baseline` times the
+REFERENCE's own AVX2 path (oracle/_ref/libfamsa_ref.so = the reference's sources +
 oracle/ref_harness.cpp) on a bounded sample of the same workload on this host's cores; the
 oracle is only the checker / the reported baseline and is never on the measured GPU path.
 """
@@ -191,13 +196,13 @@ def measure_traffic(argv):
     exe = shutil.which("rocprofv3")
     if not exe:
         return None, "rocprofv3 is not on PATH"
-    keep, skip = [], False
-    for a in argv:  # the command as it was given, without its own --pmc [value]
-        if skip and a in ("auto", "on", "off"):
-            skip = False
+    keep, skip = [], None
+    for a in argv:  # the command as it was given, without its own --pmc [value] and --dump-outputs DIR
+        if skip == "--dump-outputs" or (skip == "--pmc" and a in ("auto", "on", "off")):
+            skip = None
             continue
-        skip = a == "--pmc"
-        if not skip and not a.startswith("--pmc="):
+        skip = a if a in ("--pmc", "--dump-outputs") else None
+        if not skip and not a.startswith(("--pmc=", "--dump-outputs=")):
             keep.append(a)
     sums = {}
     for counter in ("FETCH_SIZE", "WRITE_SIZE"):
@@ -294,6 +299,30 @@ def sampled_parity(eng, tri, r0, r1, codes, offsets, n_samples=6000, seed=11):
         want = oracle.lcs(codes[o[i]:o[i + 1]], codes[o[j]:o[j + 1]])  # ref = row, partner = column
         bad += int(want != int(got[k]))
     return n_samples, bad
+
+
+DUMP_TRIANGLE_SAMPLE = 4 << 20  # positions of the triangle --dump-outputs keeps (float32: 16 MiB)
+
+
+def dump_outputs(directory, edges, tri=None, my_pairs=0):
+    """--dump-outputs DIR: what the last timed step handed to its caller, as float arrays by which two builds of the
+    library can be compared output for output (the inputs are generated from fixed seeds, so the same arguments give
+    the same files).  `mst_edges.npy`: float64 [n-1, 3] = (from, to, dist) of the tree in Prim's insertion order, as
+    returned on the host.  `lcs_triangle_sample.npy`: float32, the LCS values at DUMP_TRIANGLE_SAMPLE positions of the
+    uint16 triangle the step left in HBM (rank 0's row block), drawn once from a fixed seed and sorted -- the whole
+    block where it is not larger than that."""
+    os.makedirs(directory, exist_ok=True)
+    flat = np.stack([edges["from"].astype(np.float64), edges["to"].astype(np.float64), edges["dist"]], axis=1)
+    np.save(os.path.join(directory, "mst_edges.npy"), flat)
+    if tri is None:
+        return
+    import torch
+    if my_pairs > DUMP_TRIANGLE_SAMPLE:
+        idx = np.sort(np.random.Generator(np.random.PCG64(0xD0D0)).integers(0, my_pairs, size=DUMP_TRIANGLE_SAMPLE))
+        got = tri[torch.from_numpy(idx).to(tri.device)]
+    else:
+        got = tri[:my_pairs]
+    np.save(os.path.join(directory, "lcs_triangle_sample.npy"), got.cpu().numpy().view(np.uint16).astype(np.float32))
 
 
 def free_port():
@@ -398,12 +427,18 @@ def main():
     ap.add_argument("--order", choices=["sorted", "input"], default="sorted",
                     help="ragged workloads: FAMSA's working order (length descending) or the order as read")
     ap.add_argument("--pmc", nargs="?", const="on", default="auto", choices=["auto", "on", "off"],
-                    help="roofline.traffic: this command again under rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, one step each, after the "
+                    help="with --full: roofline.traffic: this command again under rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, one step each, after the "
                          "timed loop (one rank).  auto (default): when rocprofv3 is on PATH; on: report why if it cannot; off: traffic = null")
     ap.add_argument("--phase-timeout-s", type=float, default=600.0,
                     help="rendezvous, self-check and every other untimed phase with more than one rank: give up after this long, naming the rank")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: the sampled oracle check of the last "
+                         "step's triangle (`parity`), the reference's CPU baseline (`cpu_baseline`) and the two profiled passes behind "
+                         "roofline.traffic (--pmc).  Without it a run sets up, warms up, times its steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step returned as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: without the CPU baseline")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: without the sampled oracle check")
     ap.add_argument("--mode", choices=["ranks", "contexts"], default="ranks",
                     help="ranks (default): one process per GPU, torch.distributed over RCCL, the lcsgpu_mst_shard_* protocol; "
                          "contexts: ONE process, one engine context per GPU, lcsgpu_multi_mst_prim (the library's own "
@@ -421,6 +456,11 @@ def main():
     ap.add_argument("--self-check", action="store_true",
                     help="run the multi-rank self-check also with one rank (it always runs with more than one)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:  # a plain run: nothing but the set-up, the warm-up, the timed steps and the line
+        args.no_parity = args.no_cpu_baseline = True
+        args.pmc = "off"
     if args.workload == "family" and "--seq-len" not in sys.argv:
         args.len = 300
 
@@ -579,6 +619,8 @@ def main():
     # rank's triangle), and every rank must have ended in the same tree
     sampled, bad = (0, 0) if args.no_parity else sampled_parity(eng, tri, r0, r1, codes, offsets)
     edges = last["edges"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, edges, tri, my_pairs)
     edges_hash = edge_list_sha256(edges)
     k_ms = float(np.mean(kernel_ms)) if kernel_ms else float("nan")
     per_rank_kernel_ms = [k_ms]
@@ -654,7 +696,7 @@ def result_line(args, n, L, world, elapsed, k_ms, my_pairs, total_pairs, fused, 
     value = cells * args.steps / elapsed / 1e9
     achieved = algo_bytes / (k_ms * 1e-3) / 1e9
     valu_rate = my_ops / (k_ms * 1e-3)
-    traffic, traffic_source = None, "not measured (--pmc off, more than one rank, or no rocprofv3 on PATH)"
+    traffic, traffic_source = None, "not measured (no --full, --pmc off, more than one rank, or no rocprofv3 on PATH)"
     return {
         "metric": "lcs_gcell_updates_per_s",
         "value": value,
@@ -779,6 +821,8 @@ def main_contexts(args):
                     bad += int(oracle.lcs(codes[o[i]:o[i + 1]], codes[o[j]:o[j + 1]]) != int(got[a, b]))
     assert bad == 0, f"{bad} of {sampled} sampled pairs differ from the oracle"
     assert len(edges) == n - 1 and (edges["from"] < edges["to"]).all()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, edges)  # the triangles stay inside the library in this mode
     my_pairs = total_pairs // N
     out = result_line(args, n, L, N, elapsed, float(max(per_ctx)), my_pairs, total_pairs, False, None,
                       parallelism=f"rowblock{N}, one process, {N} contexts (lcsgpu_multi_mst_prim)",

@@ -6,8 +6,8 @@ ROOT=$(pwd)
 mkdir -p gpurun_out
 timeout 1500 python -m pytest tests -m gpu -x -q 2>&1 | grep -E "passed|failed|rror" | tail -5 > gpurun_out/full_gpu_suite.txt
 cat gpurun_out/full_gpu_suite.txt
-python bench.py > gpurun_out/bench_r06_final.json 2> gpurun_out/bench_r06_final.err
-tail -c 600 gpurun_out/bench_r06_final.json
+python bench.py --full > /tmp/bench_r06_final.json 2> /tmp/bench_r06_final.err
+tail -c 600 /tmp/bench_r06_final.json
 bash scripts/profile_round.sh r06 > /dev/null 2>&1
 bash scripts/gpu_r06_small.sh > gpurun_out/small_r06.txt 2>&1
 bash scripts/gpu_r06_c5_runs.sh > /dev/null 2>&1

@@ -216,7 +216,7 @@ def _bench(args, world, torchrun=True):
 def test_bench_step_ends_in_the_same_tree_for_every_rank_count():
     """bench.py --gpus N (ranks sharing cuda:0, gloo exchange): the MST edge-list hash it prints does not
     depend on N, and the sampled oracle check of the timed triangle passes inside it."""
-    args = ["--steps", "1", "--warmup", "1", "--n-seqs", "5000", "--seq-len", "120", "--no-cpu-baseline"]
+    args = ["--steps", "1", "--warmup", "1", "--n-seqs", "5000", "--seq-len", "120", "--full", "--no-cpu-baseline"]
     one = _bench(args, 1)
     two = _bench(args, 2)  # under torch.distributed.run, as the driver starts it
     assert one["mst"]["edges_sha256"] == two["mst"]["edges_sha256"]
@@ -230,7 +230,7 @@ def test_bench_starts_its_own_ranks():
     N > 1 the same way gets): the script starts its N ranks itself, runs the fail-closed self-check (the ranks' sharded
     tree on a 2000-sequence family set against every rank's single-context tree) and prints one line with the per-rank
     kernel times; the hash equals the one-rank hash."""
-    args = ["--steps", "1", "--warmup", "1", "--n-seqs", "5000", "--seq-len", "120", "--no-cpu-baseline"]
+    args = ["--steps", "1", "--warmup", "1", "--n-seqs", "5000", "--seq-len", "120", "--full", "--no-cpu-baseline"]
     one = _bench(args, 1)
     three = _bench(args + ["--emulate-ranks-on-one-gpu"], 3, torchrun=False)
     for rec, w in ((three, 3),):
@@ -248,7 +248,7 @@ def test_bench_starts_its_own_ranks():
 def test_bench_contexts_mode():
     """--mode contexts: one process, N contexts, lcsgpu_multi_mst_prim -- the library's own multi-GPU path -- with its
     self-check; same tree as the ranks mode, per-context kernel times, the transport report in the line."""
-    args = ["--steps", "1", "--warmup", "1", "--n-seqs", "5000", "--seq-len", "120", "--no-cpu-baseline"]
+    args = ["--steps", "1", "--warmup", "1", "--n-seqs", "5000", "--seq-len", "120", "--full", "--no-cpu-baseline"]
     one = _bench(args, 1)
     ctx3 = _bench(args + ["--mode", "contexts", "--emulate-ranks-on-one-gpu"], 3, torchrun=False)
     assert ctx3["mst"]["edges_sha256"] == one["mst"]["edges_sha256"] and ctx3["n_gpus"] == 3
@@ -263,10 +263,30 @@ def test_bench_with_the_real_collective_on_one_rank():
     torch.distributed initialised with the nccl (= RCCL) backend, all_gather_into_tensor on device tensors, the
     hand-off between the engine's stream and torch's -- so RCCL initialisation and the stream ordering run on an
     MI355X in every GPU test run, not for the first time on an 8-GPU node.  Same tree as without it."""
-    args = ["--steps", "2", "--warmup", "1", "--n-seqs", "6000", "--seq-len", "120", "--no-cpu-baseline"]
+    args = ["--steps", "2", "--warmup", "1", "--n-seqs", "6000", "--seq-len", "120", "--full", "--no-cpu-baseline"]
     plain = _bench(args, 1)
     forced = _bench(args + ["--force-collective", "--self-check"], 1)
     assert forced["config"]["exchange"].startswith("nccl") and plain["config"]["exchange"].startswith("none")
     assert forced["ranks"]["rccl_ranks"] == 1 and forced["ranks"]["self_check"]["ranks_agree"]
     assert forced["mst"]["edges_sha256"] == plain["mst"]["edges_sha256"]
     assert forced["mst"]["rounds"] == plain["mst"]["rounds"] and forced["parity"]["mismatches"] == 0
+
+
+def test_bench_plain_run_and_dumped_outputs(engine, tmp_path):
+    """A plain run (no --full) times exactly --steps steps and leaves the checks that take runs of their own out of the
+    line; --dump-outputs writes what the last timed step returned: the tree in Prim's order (the hash in the line is the
+    hash of these edges) and the triangle (1 999 000 pairs: below the sample size, so all of it), both equal to what
+    one context computes on the same set."""
+    out = str(tmp_path / "dump")
+    rec = _bench(["--steps", "2", "--warmup", "0", "--n-seqs", "2000", "--seq-len", "120", "--dump-outputs", out], 1)
+    assert rec["steps"] == 2 and rec["warmup"] == 0 and rec["ms_per_step"] > 0
+    assert rec["parity"]["sampled_pairs"] == 0 and "cpu_baseline" not in rec and rec["roofline"]["traffic"] is None
+    assert sorted(os.listdir(out)) == ["lcs_triangle_sample.npy", "mst_edges.npy"]
+    flat, tri = np.load(os.path.join(out, "mst_edges.npy")), np.load(os.path.join(out, "lcs_triangle_sample.npy"))
+    assert flat.dtype == np.float64 and flat.shape == (1999, 3) and tri.dtype == np.float32 and tri.shape == (1999000,)
+    engine.upload(*seqio.synth_uniform(2000, 120))
+    want = engine.mst_prim(1)
+    got = np.zeros(len(flat), dtype=want.dtype)
+    got["from"], got["to"], got["dist"] = flat[:, 0], flat[:, 1], flat[:, 2]
+    assert _same(got, want) and edge_list_sha256(got) == rec["mst"]["edges_sha256"]
+    assert (tri == engine.lcs_triangle(dtype=np.uint16)).all()

@@ -17,8 +17,9 @@
 // the medoid in slot mm (kept in step with the swaps so that the reference's updateAssignment scan
 // is k coalesced loads instead of k scattered triangle entries per lane).
 //
-// Shapes: 1 <= n - k <= 2048 non-medoids (every position's state in the registers of one workgroup), k <= 1024; the
-// host side answers LCSGPU_E_UNSUPPORTED beyond that and the caller searches on the host.  (Rounds 1-5 also carried:
+// Shapes: 1 <= n - k <= 2048 non-medoids (every position's state in the registers of one workgroup), k <= 1024; beyond
+// that lcsgpu_clarans[_batch] answer LCSGPU_E_UNSUPPORTED, and lcsgpu_clarans_large[_batch] run the sample in
+// clarans_large_chain_kernel (below: the same chain with its state in memory).  (Rounds 1-5 also carried:
 // a launch per round with a workgroup per pending step -- all steps up to the next accept evaluated at once from the
 // same state --, its two-launch form, an evaluation with per-slot lists and a one-XCD persistent kernel; each was
 // measured slower than what replaced it -- profiles/clarans_rounds_r03.txt, clarans_rounds_r04.txt,
@@ -844,8 +845,543 @@ __global__ __launch_bounds__(512, 4) void clarans_chain_kernel(const ClaransChai
         st[ST_ROUNDS] = R.accepts;
         st[ST_FRESH] = R.fresh;
         st[ST_COST] = __float_as_int(R.cost);
-        st[ST_ERR] = 0;
-        st[ST_MORE_DRAWS] = status == 2;
+        st[ST_MORE_DRAWS] = status == 2; // (ST_ERR is the host's to clear: a set error survives the launches that follow)
+        st[ST_OFF] = R.off;
+        st[ST_FIRST] = R.first;
+        st[ST_N_ROUNDS] = R.n_groups;
+        st[ST_N_STEPS] = R.n_steps;
+        st[ST_N_USEFUL] = R.n_useful;
+        st[ST_N_NOB] = R.n_nob;
+        st[ST_N_NOP] = R.n_nop;
+        st[ST_ITER] = iter;
+        st[ST_BEST] = __float_as_int(best);
+        st[ST_NEED_INIT] = need_init;
+        st[ST_TICKS] += (int)(wall_clock64() - t_begin);
+        st[ST_CU] = (int)((__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (3 << 11)) << 8) | (__builtin_amdgcn_s_getreg((4 << 0) | (8 << 6) | (7 << 11))));
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// THE SAME CHAIN FOR SAMPLES BEYOND THE REGISTERS OF ONE WORKGROUP (clarans_large_chain_kernel): more than 2048
+// non-medoids or more than 1024 medoids, up to CLARANS_LARGE_MAX_MEMBERS members.
+//
+// Still one workgroup per chain and nothing any other workgroup waits for.  What the chain kernel keeps in registers
+// stays in memory here -- st[pos], cand[pos], DMt, and dn_member[member] = the member's distance to its medoid (0 for a
+// medoid), the table of the flags phase -- and every phase walks the non-medoids in slices: the working set of a chain
+// (a few rows of D, 24 bytes per position) stays in the L2.  The float order is the chain kernel's, which is the
+// reference's: a slot's delta is ONE accumulator that takes the non-medoids' addends in ascending position, carried
+// from slice to slice; the accept's 1 + (n - k) cost addends go through cost_accumulate, which chunks by 2048.
+//
+// Slots: an evaluation takes the slots in batches of 1024 (8 waves x 2 slots per lane, the chain kernel's widest
+// form); each batch sums its X_s (LDS), drops out if none of its slots can go negative, and otherwise walks all
+// slices for its slots.  The minimum is taken batch by batch in ascending slot order with a strict '<': the first
+// minimum, the earliest slot among equals.
+//
+// THE PRUNING BOUND SCALES WITH THE NUMBER OF TERMS.  As in evaluate_step: delta[s] = X_s + Y exactly, X_s >= 0 the
+// sum of slot s's own addends, Y <= 0 the sum of the addends every slot takes; a float sum of m terms in any order is
+// off by at most g (X_s + |Y|), g = m u / (1 - m u), u = 2^-24, and the sums of equal-signed terms computed here (X^,
+// Y^) are within the factor (1 +- g) of X_s and |Y|.  The reference's delta is positive if X_s (1 - g) > |Y| (1 + g).
+// From X^ > c |Y^| follows X_s > c |Y| (1 - g) / (1 + g), so c >= ((1 + g) / (1 - g))^2 ~ 1 + 4 g is what is needed:
+// 5.2e-4 at m = 2049 (the chain kernel's 1.002 is four times that), but 7.8e-3 at m = 32768 -- 1.002 would drop slots
+// that can be negative.  Here c = 1 + 16 m 2^-24 with m = n - k + 1 (one more than the terms a slot can have): four
+// times the margin needed, at every size (1.00195 at 2049 terms, 1.03125 at 32768).
+//
+// A launch ends for a chain when it is done, when its pre-drawn positions run out, or when its time slice is over
+// (looked at once per group of steps, between groups: where a launch ends cannot change which step is accepted); all
+// state is in memory, so the next launch goes on where this one stood.
+namespace {
+
+struct LargeShared {
+    float4 s_e[1024];    // 16 KB  a slice's entries / cost_accumulate's staging
+    float4 s_we[8][128]; // 16 KB  per wave: the entries of a sub-slice that can change one of its slots
+    float s_x[CLARANS_MAX_MEDOIDS + 8]; // X_s of the batch's slots, then their "in P" flags; [1024]: Y
+    float s_v[8];
+    int s_k[8];
+    unsigned s_flag[2][9];
+};
+
+// the first minimum over the workgroup: a valid index beats none, then the smaller value, then the smaller index;
+// the result is in every thread
+__device__ __forceinline__ void block_first_min_valid(float& v, int& i, LargeShared& sh)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    wave_first_min_valid(v, i);
+    if (lane == 0) {
+        sh.s_v[wave] = v;
+        sh.s_k[wave] = i;
+    }
+    __syncthreads();
+    v = sh.s_v[0];
+    i = sh.s_k[0];
+#pragma unroll
+    for (int w = 1; w < 8; ++w) {
+        const float v2 = sh.s_v[w];
+        const int k2 = sh.s_k[w];
+        if (k2 != INT_MAX && (i == INT_MAX || v2 < v || (v2 == v && k2 < i))) { v = v2; i = k2; }
+    }
+    __syncthreads(); // (the slots are free for the next call)
+}
+
+__device__ __forceinline__ int ld_cand(const ClaransArgs& a, int i) { return __hip_atomic_load(a.cand + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+__device__ __forceinline__ int ld_cand_uniform(const ClaransArgs& a, int i) { return __builtin_amdgcn_readfirstlane(ld_cand(a, i)); }
+
+// The two nearest slots of the position pos by the whole wave (pos, d_swap, swap_slot wave-uniform): "first minimum
+// over the slots, then first minimum over the rest" -- what the sequential scan of Clustering.cpp:262-305 arrives
+// at.  Slot swap_slot (if >= 0) counts with the distance d_swap instead of what DMt holds.
+__device__ __forceinline__ float4 wave_two_nearest(const ClaransArgs& a, int pos, int swap_slot, float d_swap)
+{
+    const int lane = threadIdx.x & 63, k = a.n_medoids, n = a.n_elems;
+    const float* col = a.DMt + pos;
+    float v[2];
+    int idx[2];
+    int skip = -1;
+#pragma unroll
+    for (int pass = 0; pass < 2; ++pass) {
+        float bv = FLT_MAX;
+        int bi = INT_MAX;
+        for (int m0 = 0; m0 < k; m0 += 256) {
+            float dv[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int mm = m0 + 64 * q + lane;
+                dv[q] = mm < k ? (mm == swap_slot ? d_swap : col[(size_t)mm * n]) : FLT_MAX;
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int mm = m0 + 64 * q + lane;
+                if (mm < k && mm != skip && (dv[q] < bv || bi == INT_MAX)) { bv = dv[q]; bi = mm; }
+            }
+        }
+        wave_first_min_valid(bv, bi);
+        v[pass] = bv;
+        idx[pass] = bi;
+        skip = bi;
+    }
+    const bool has1 = idx[0] != INT_MAX && v[0] < FLT_MAX, has2 = idx[1] != INT_MAX && v[1] < FLT_MAX;
+    return pack_state(has1 ? v[0] : FLT_MAX, has2 ? v[1] : FLT_MAX, has1 ? idx[0] : -1, has2 ? idx[1] : -1);
+}
+
+// Start of one local search (chain_init for any size): DMt, the assignments, the initial cost's addends, dn_member
+__device__ __forceinline__ void large_init(const ClaransArgs& a, float* dn_member)
+{
+    constexpr int PER = 4;
+    const int k = a.n_medoids, n = a.n_elems, tid = threadIdx.x;
+    for (int p0 = k; p0 < n; p0 += 512 * PER) {
+        int y[PER];
+        Nearest2 nb[PER];
+#pragma unroll
+        for (int u = 0; u < PER; ++u) {
+            const int pos = p0 + tid + 512 * u;
+            y[u] = pos < n ? ld_cand(a, pos) : 0;
+        }
+        for (int mm = 0; mm < k; ++mm) {
+            const float* row = a.D + (size_t)ld_cand_uniform(a, mm) * (size_t)n;
+            float d[PER];
+#pragma unroll
+            for (int u = 0; u < PER; ++u) d[u] = row[y[u]];
+#pragma unroll
+            for (int u = 0; u < PER; ++u) {
+                const int pos = p0 + tid + 512 * u;
+                if (pos < n) {
+                    a.DMt[(size_t)mm * n + pos] = d[u];
+                    nb[u].feed(d[u], mm);
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < PER; ++u) {
+            const int pos = p0 + tid + 512 * u;
+            if (pos >= n) continue;
+            a.st[pos] = pack_state(nb[u].dn, nb[u].ds, nb[u].an, nb[u].as);
+            a.cost_log[pos - k] = nb[u].dn;
+            dn_member[y[u]] = nb[u].dn;
+        }
+    }
+    for (int mm = tid; mm < k; mm += 512) dn_member[ld_cand(a, mm)] = 0.0f;
+}
+
+// evaluate_step for any size: deltas[slot] of the member x drawn at position xx and their first minimum over the free
+// slots that can go negative.  The results are in every thread.
+__device__ __forceinline__ void evaluate_step_large(const ClaransArgs& a, int xx, int x, LargeShared& sh, float& best_out, int& bk_out, int& why_out)
+{
+    constexpr int KPT = 2, BATCH = CLARANS_MAX_MEDOIDS, SLICE = 1024, SUB = 128;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int k = a.n_medoids, n = a.n_elems, cnt = n - k;
+    const uint64_t lt_mask = lane ? (~0ull >> (64 - lane)) : 0ull;
+    const float* rowx = a.D + (size_t)x * (size_t)n;
+    const float scale = 1.0f + 16.0f * (float)(cnt + 1) * 0x1p-24f; // see above
+    const float4 nothing = make_float4(0.0f, 0.0f, __int_as_float(-1), 0.0f);
+    float best = 0.0f, Y = 0.0f;
+    int bk = INT_MAX, why = WHY_NO_P;
+    for (int s_lo = 0; s_lo < k; s_lo += BATCH) {
+        const int nb = min(BATCH, k - s_lo);
+        for (int s = tid; s < nb; s += 512) sh.s_x[s] = 0.0f;
+        if (s_lo == 0 && tid == 0) sh.s_x[BATCH] = 0.0f;
+        __syncthreads();
+        // X_s of the batch's slots (and Y with the first batch), in any order
+        float ysum = 0.0f;
+        for (int t0 = 0; t0 < cnt; t0 += 2048) {
+            float d[4];
+            float4 s4[4];
+            bool on[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int t = t0 + tid + 512 * u;
+                on[u] = t < cnt && k + t != xx;
+                d[u] = on[u] ? rowx[ld_cand(a, k + t)] : 0.0f;
+                s4[u] = on[u] ? a.st[k + t] : nothing;
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (!on[u]) continue;
+                const float dn = s4[u].x, ds = s4[u].y;
+                const float change = __fsub_rn(d[u], dn);
+                if (change < 0.0f) ysum += change;
+                else {
+                    const int rel = __float_as_int(s4[u].z) - s_lo;
+                    const float m = ds < d[u] ? ds : d[u];
+                    if (rel >= 0 && rel < nb) atomicAdd(&sh.s_x[rel], __fsub_rn(m, dn));
+                }
+            }
+        }
+        if (s_lo == 0) {
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) ysum += __shfl_xor(ysum, o);
+            if (lane == 0 && ysum != 0.0f) atomicAdd(&sh.s_x[BATCH], ysum);
+        }
+        __syncthreads();
+        if (s_lo == 0) {
+            Y = sh.s_x[BATCH];
+            if (!(Y < 0.0f)) { // no member is closer to the candidate than to its medoid: no delta is negative
+                why = WHY_NO_B;
+                __syncthreads(); // (everybody has read Y before the next evaluation clears it)
+                break;
+            }
+        }
+        const float bound = -Y * scale;
+        bool any_p = false;
+        for (int s = tid; s < nb; s += 512) { // (X_s is read and replaced by its flag by one thread only)
+            const bool in_p = s_lo + s >= a.n_fixed && !(sh.s_x[s] > bound);
+            sh.s_x[s] = in_p ? 1.0f : 0.0f;
+            any_p |= in_p;
+        }
+        if (!__syncthreads_or(any_p ? 1 : 0)) continue;
+        why = WHY_WALKED;
+        // the exact sums of the batch's slots in P: wave w owns the slots [klo, khi)
+        const int klo = s_lo + wave * (BATCH / 8), khi = min(s_lo + nb, klo + BATCH / 8);
+        float acc[KPT];
+        int slot[KPT];
+#pragma unroll
+        for (int q = 0; q < KPT; ++q) {
+            acc[q] = 0.0f;
+            slot[q] = klo + lane + 64 * q;
+        }
+        for (int c0 = 0; c0 < cnt; c0 += SLICE) {
+            const int hcnt = min(SLICE, cnt - c0);
+#pragma unroll
+            for (int u = 0; u < SLICE / 512; ++u) {
+                const int t = tid + 512 * u, pos = k + c0 + t;
+                if (t >= hcnt) continue;
+                float4 e = nothing;
+                if (pos != xx) {
+                    const float d = rowx[ld_cand(a, pos)];
+                    const float4 s4 = a.st[pos];
+                    const float dn = s4.x, ds = s4.y;
+                    const float m = ds < d ? ds : d; // std::min(dxy, ds)
+                    const float change = __fsub_rn(d, dn);
+                    const int rel = __float_as_int(s4.z) - s_lo;
+                    // (an own addend of a slot outside the batch or outside P takes no part)
+                    if (change < 0.0f) e = make_float4(__fsub_rn(m, dn), change, s4.z, 0.0f);
+                    else if (rel >= 0 && rel < nb && sh.s_x[rel] != 0.0f) e = make_float4(__fsub_rn(m, dn), 0.0f, s4.z, 0.0f);
+                }
+                sh.s_e[t] = e;
+            }
+            __syncthreads();
+            for (int s0 = 0; s0 < hcnt; s0 += SUB) {
+                float4 e[SUB / 64];
+#pragma unroll
+                for (int u = 0; u < SUB / 64; ++u) {
+                    const int t = s0 + 64 * u + lane;
+                    e[u] = t < hcnt ? sh.s_e[t] : nothing;
+                }
+                int m = 0;
+#pragma unroll
+                for (int u = 0; u < SUB / 64; ++u) {
+                    const int nn = __float_as_int(e[u].z);
+                    const bool mine = e[u].y < 0.0f || (nn >= klo && nn < khi);
+                    const uint64_t mask = __ballot(mine);
+                    if (mine) sh.s_we[wave][m + __popcll(mask & lt_mask)] = e[u];
+                    m += __popcll(mask);
+                }
+                __builtin_amdgcn_wave_barrier(); // same wave: its LDS writes are performed before its later reads
+                int i = 0;
+                for (; i + 8 <= m; i += 8) {
+                    float4 f[8];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) f[u] = sh.s_we[wave][i + u];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) {
+                        const int nn = __float_as_int(f[u].z);
+#pragma unroll
+                        for (int q = 0; q < KPT; ++q) acc[q] = __fadd_rn(acc[q], slot[q] == nn ? f[u].x : f[u].y);
+                    }
+                }
+                for (; i < m; ++i) {
+                    const float4 f = sh.s_we[wave][i];
+                    const int nn = __float_as_int(f.z);
+#pragma unroll
+                    for (int q = 0; q < KPT; ++q) acc[q] = __fadd_rn(acc[q], slot[q] == nn ? f.x : f.y);
+                }
+                __builtin_amdgcn_wave_barrier();
+            }
+            __syncthreads();
+        }
+        // std::min_element over the batch's slots of P, then over the batches in ascending order
+        float bv = 0.0f;
+        int bi = INT_MAX;
+#pragma unroll
+        for (int q = 0; q < KPT; ++q)
+            if (slot[q] < khi && sh.s_x[slot[q] - s_lo] != 0.0f && (bi == INT_MAX || acc[q] < bv)) { bv = acc[q]; bi = slot[q]; }
+        block_first_min_valid(bv, bi, sh);
+        if (bi != INT_MAX && (bk == INT_MAX || bv < best)) { best = bv; bk = bi; }
+    }
+    best_out = best;
+    bk_out = bk;
+    why_out = why;
+}
+
+// clarans_search_body for any size.  Returns 1: the local search is over, 2: out of pre-drawn positions, 0: the time slice is over.
+__device__ __forceinline__ int large_search_body(const ClaransArgs& a, float* dn_member, SearchRegs& R, LargeShared& sh, long long slice_ticks, long long t_begin)
+{
+    constexpr int Q = 8;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int k = a.n_medoids, n = a.n_elems, corrected = a.corrected, cnt = n - k;
+    int P = R.P, off = R.off, first = R.first, accepts = R.accepts;
+    float cost = R.cost;
+    int n_groups = R.n_groups, n_steps = R.n_steps, n_useful = R.n_useful, n_nob = R.n_nob, n_nop = R.n_nop;
+    float* s_f = reinterpret_cast<float*>(sh.s_e);
+    float* s_nz = reinterpret_cast<float*>(sh.s_we);
+    if (R.fresh) cost = cost_accumulate(a.cost_log, cnt, cost, s_f, s_nz); // the initial cost (Clustering.cpp:49-79)
+    int status = 0, expired = 0;
+    for (unsigned g = 0;; ++g) {
+        const int W = window_size(corrected, first);
+        if (off >= W) { // `corrected` steps (corrected - 1 after an accept) without an accept
+            P += W;
+            off = 0;
+            status = 1;
+            break;
+        }
+        const int avail = a.draws_len - (P + off);
+        if (avail <= 0) {
+            status = 2;
+            break;
+        }
+        if (expired) break;
+        const int qn = min(Q, min(W - off, avail));
+        const int32_t* dr = a.draws + P + off;
+        // ---- the group's flags, member by member: the rows of D and dn_member as they lie in memory ----
+        int x[Q];
+#pragma unroll
+        for (int c = 0; c < Q; ++c) x[c] = ld_cand_uniform(a, dr[min(c, qn - 1)]);
+        unsigned m = 0;
+        for (int i0 = 0; i0 < n; i0 += 512) {
+            const int i = min(i0 + tid, n - 1);
+            const float dnm = dn_member[i];
+            float d[Q];
+#pragma unroll
+            for (int c = 0; c < Q; ++c) d[c] = a.D[(size_t)x[c] * (size_t)n + i];
+#pragma unroll
+            for (int c = 0; c < Q; ++c)
+                if (i != x[c] && __fsub_rn(d[c], dnm) < 0.0f) m |= 1u << c;
+        }
+        unsigned wm = 0;
+#pragma unroll
+        for (int s = 0; s < Q; ++s)
+            if (__ballot((m >> s) & 1u)) wm |= 1u << s;
+        if (lane == 0) sh.s_flag[g & 1][wave] = wm;
+        if (tid == 0) sh.s_flag[g & 1][8] = wall_clock64() - t_begin > slice_ticks;
+        __syncthreads();
+        expired = __builtin_amdgcn_readfirstlane((int)sh.s_flag[g & 1][8]);
+        unsigned flags = 0;
+#pragma unroll
+        for (int w = 0; w < 8; ++w) flags |= sh.s_flag[g & 1][w];
+        flags = (unsigned)__builtin_amdgcn_readfirstlane((int)flags) & ((1u << qn) - 1u);
+        // ---- the flagged steps, in order, up to the first accept ----
+        int acc_s = -1, mm_new = 0;
+        for (unsigned todo = flags; todo; todo &= todo - 1) {
+            const int s = __builtin_ctz(todo);
+            const int xx = dr[s];
+            float best = 0.0f;
+            int bk = INT_MAX, why = WHY_WALKED;
+            evaluate_step_large(a, xx, ld_cand_uniform(a, xx), sh, best, bk, why);
+            mm_new = __builtin_amdgcn_readfirstlane(bk);
+            if (why == WHY_NO_P) ++n_nop;
+            if (__int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(best))) < 0.0f) {
+                acc_s = s;
+                break;
+            }
+        }
+        const int upto = acc_s >= 0 ? acc_s + 1 : qn;
+        ++n_groups;
+        n_steps += qn;
+        n_useful += upto;
+        n_nob += __popc(~flags & ((1u << upto) - 1u));
+        if (acc_s < 0) {
+            off += qn;
+            continue;
+        }
+        // ---- the accept (Clustering.cpp:124-238, branch by branch) ----
+        const int xx_acc = dr[acc_s], x_acc = ld_cand_uniform(a, xx_acc), m_old = ld_cand_uniform(a, mm_new);
+        // the position that receives the replaced medoid: distances to the new medoid set, a fresh assignment
+        float4 xx_state;
+        {
+            float v1 = FLT_MAX, v2 = FLT_MAX;
+            int i1 = INT_MAX, i2 = INT_MAX;
+            for (int mm = tid; mm < k; mm += 512) {
+                const float dv = a.D[sq_at(n, mm == mm_new ? x_acc : ld_cand(a, mm), m_old)];
+                a.DMt[(size_t)mm * n + xx_acc] = dv;
+                if (dv < v1 || i1 == INT_MAX) { v1 = dv; i1 = mm; }
+            }
+            block_first_min_valid(v1, i1, sh);
+            for (int mm = tid; mm < k; mm += 512) {
+                if (mm == i1) continue;
+                const float dv = a.DMt[(size_t)mm * n + xx_acc]; // (this thread's own store)
+                if (dv < v2 || i2 == INT_MAX) { v2 = dv; i2 = mm; }
+            }
+            block_first_min_valid(v2, i2, sh);
+            const bool has1 = i1 != INT_MAX && v1 < FLT_MAX, has2 = i2 != INT_MAX && v2 < FLT_MAX;
+            xx_state = pack_state(has1 ? v1 : FLT_MAX, has2 ? v2 : FLT_MAX, has1 ? i1 : -1, has2 ? i2 : -1);
+        }
+        // every other non-medoid keeps, moves or re-derives its two nearest slots; a position that has to look at all
+        // k slots again is taken by its wave (wave_two_nearest)
+        for (int t0 = wave * 64; t0 < cnt; t0 += 512) {
+            const int t = t0 + lane, pos = k + t;
+            const bool on = t < cnt;
+            float addend = 0.0f, d_new = 0.0f;
+            float4 s4 = make_float4(0.f, 0.f, 0.f, 0.f);
+            bool need = false;
+            int y = 0;
+            if (on && pos != xx_acc) {
+                y = ld_cand(a, pos);
+                d_new = a.D[sq_at(n, x_acc, y)];
+                s4 = a.st[pos];
+                apply_accept_to_position(s4, d_new, mm_new, addend, need);
+            }
+            for (unsigned long long rs = __ballot(need); rs; rs &= rs - 1) {
+                const int rl = (int)__builtin_ctzll(rs);
+                const float dnw_r = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(d_new), rl));
+                const float4 r4 = wave_two_nearest(a, k + t0 + rl, mm_new, dnw_r);
+                if (lane == rl) s4 = r4;
+            }
+            if (!on) continue;
+            if (pos == xx_acc) {
+                a.cost_log[0] = -a.st[pos].x; // the new medoid leaves the sum first
+                a.st[pos] = xx_state;
+                a.cost_log[1 + t] = xx_state.x;
+                dn_member[m_old] = xx_state.x;
+            } else {
+                a.st[pos] = s4;
+                a.cost_log[1 + t] = addend;
+                a.DMt[(size_t)mm_new * n + pos] = d_new;
+                dn_member[y] = s4.x;
+            }
+        }
+        if (tid == 0) dn_member[x_acc] = 0.0f;
+        __syncthreads(); // (the order's old entries have been read; the log is where cost_accumulate reads it)
+        if (tid == 0) {
+            __hip_atomic_store(a.cand + mm_new, x_acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_store(a.cand + xx_acc, m_old, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+        __syncthreads();
+        cost = cost_accumulate(a.cost_log, 1 + cnt, cost, s_f, s_nz);
+        P += off + acc_s + 1;
+        off = 0;
+        first = 0;
+        ++accepts;
+    }
+    __syncthreads();
+    R.P = P;
+    R.off = off;
+    R.first = first;
+    R.accepts = accepts;
+    R.fresh = 0;
+    R.cost = cost;
+    R.n_groups = n_groups;
+    R.n_steps = n_steps;
+    R.n_useful = n_useful;
+    R.n_nob = n_nob;
+    R.n_nop = n_nop;
+    return status;
+}
+
+} // namespace
+
+__global__ __launch_bounds__(512, 4) void clarans_large_chain_kernel(const ClaransChain* __restrict__ chains, long long slice_ticks)
+{
+    const ClaransChain& ch = chains[blockIdx.x];
+    const ClaransArgs& a = ch.a;
+    const long long t_begin = wall_clock64();
+    __shared__ LargeShared sh;
+    __shared__ int s_better;
+    const int tid = threadIdx.x, k = a.n_medoids, n = a.n_elems;
+    SearchRegs R;
+    R.P = __builtin_amdgcn_readfirstlane(a.state[ST_P]);
+    R.off = __builtin_amdgcn_readfirstlane(a.state[ST_OFF]);
+    R.first = __builtin_amdgcn_readfirstlane(a.state[ST_FIRST]);
+    R.accepts = __builtin_amdgcn_readfirstlane(a.state[ST_ROUNDS]);
+    R.fresh = __builtin_amdgcn_readfirstlane(a.state[ST_FRESH]);
+    R.cost = __int_as_float(a.state[ST_COST]);
+    R.n_groups = a.state[ST_N_ROUNDS];
+    R.n_steps = a.state[ST_N_STEPS];
+    R.n_useful = a.state[ST_N_USEFUL];
+    R.n_nob = a.state[ST_N_NOB];
+    R.n_nop = a.state[ST_N_NOP];
+    int iter = __builtin_amdgcn_readfirstlane(a.state[ST_ITER]), need_init = __builtin_amdgcn_readfirstlane(a.state[ST_NEED_INIT]);
+    float best = __int_as_float(a.state[ST_BEST]); // (kept by thread 0)
+    int status = 0;
+    while (iter < ch.num_local) {
+        if (need_init) {
+            // the order before this search: position i takes what position perm[i] held (the first search starts from
+            // 0, 1, 2, ...); the new order is put together in the states' array, which the search's start writes anew
+            const int32_t* perm = ch.perm + (size_t)iter * (size_t)n;
+            int32_t* tmp = reinterpret_cast<int32_t*>(a.st);
+            for (int i = tid; i < n; i += 512) {
+                const int from = perm[i];
+                tmp[i] = iter == 0 ? from : ld_cand(a, from);
+            }
+            __syncthreads();
+            for (int i = tid; i < n; i += 512) __hip_atomic_store(a.cand + i, tmp[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __syncthreads();
+            large_init(a, ch.dn_member);
+            __syncthreads();
+            R.off = 0;
+            R.first = 1;
+            R.fresh = 1;
+            R.cost = 0.0f;
+            need_init = 0;
+        }
+        status = large_search_body(a, ch.dn_member, R, sh, slice_ticks, t_begin);
+        if (status != 1) break;
+        // the search is over: its medoids stand if it is strictly cheaper than the best so far (Clustering.cpp:239-257)
+        if (tid == 0) {
+            s_better = R.cost < best;
+            if (R.cost < best) best = R.cost;
+        }
+        __syncthreads();
+        if (s_better)
+            for (int mm = tid; mm < k; mm += 512) ch.best[mm] = ld_cand(a, mm);
+        __syncthreads();
+        ++iter;
+        need_init = 1;
+    }
+    if (tid == 0) {
+        int32_t* st = a.state;
+        st[ST_P] = R.P;
+        st[ST_DONE] = iter >= ch.num_local;
+        st[ST_ROUNDS] = R.accepts;
+        st[ST_FRESH] = R.fresh;
+        st[ST_COST] = __float_as_int(R.cost);
+        st[ST_MORE_DRAWS] = status == 2; // (ST_ERR stays as it is)
         st[ST_OFF] = R.off;
         st[ST_FIRST] = R.first;
         st[ST_N_ROUNDS] = R.n_groups;
@@ -910,6 +1446,15 @@ hipError_t launch_clarans_chains(const ClaransChain* chains, int n_chains, int m
     const long long ticks = slice_us > 0 ? (long long)slice_us * 100 : LLONG_MAX; // wall_clock64: 100 MHz
     if (kpt <= 1) hipLaunchKernelGGL(clarans_chain_kernel<1>, dim3(n_chains), dim3(512), 0, stream, chains, ticks);
     else hipLaunchKernelGGL(clarans_chain_kernel<2>, dim3(n_chains), dim3(512), 0, stream, chains, ticks);
+    return hipGetLastError();
+}
+
+// the chains beyond the chain kernel's shapes, every one in its own workgroup for at most `slice_us` microseconds (0 = no limit)
+hipError_t launch_clarans_large_chains(const ClaransChain* chains, int n_chains, int slice_us, hipStream_t stream)
+{
+    if (n_chains <= 0) return hipSuccess;
+    const long long ticks = slice_us > 0 ? (long long)slice_us * 100 : LLONG_MAX; // wall_clock64: 100 MHz
+    hipLaunchKernelGGL(clarans_large_chain_kernel, dim3(n_chains), dim3(512), 0, stream, chains, ticks);
     return hipGetLastError();
 }
 

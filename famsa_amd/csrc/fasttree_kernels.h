@@ -29,10 +29,16 @@ struct ClaransChain {
     int32_t* best;        // [n_medoids] the medoids of the cheapest search so far
     int64_t tri0;         // element offset of the sample's packed LCS triangle in the launch's triangle buffer
     int32_t num_local;
+    float* dn_member;     // [n_elems] by MEMBER: its distance to its medoid, 0 for a medoid (clarans_large_chain_kernel only)
 };
+// samples beyond CLARANS_MAX_MEDOIDS / CLARANS_MAX_NONMEDOIDS run in clarans_large_chain_kernel, up to this many members: the
+// float matrix of a sample is 4.3 GB then, and (n - k) * k stays inside the reference's int (Clustering.cpp:21)
+constexpr int CLARANS_LARGE_MAX_MEMBERS = 32768;
 hipError_t launch_subset_distances_batch(const void* lcs, int elem_size, const ClaransChain* chains, int n_chains, int max_n,
                                          const uint32_t* lens, const float* pow_f32, int kind, hipStream_t stream);
 // every chain in its own workgroup, to its end -- or until its pre-drawn positions run out, or for slice_us microseconds (0 = no limit)
 hipError_t launch_clarans_chains(const ClaransChain* chains, int n_chains, int max_medoids, int slice_us, hipStream_t stream);
+// the same for chains of any shape up to CLARANS_LARGE_MAX_MEMBERS (state in memory, walked in slices)
+hipError_t launch_clarans_large_chains(const ClaransChain* chains, int n_chains, int slice_us, hipStream_t stream);
 
 } // namespace lcsgpu

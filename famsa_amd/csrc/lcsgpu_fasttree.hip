@@ -548,8 +548,12 @@ int lcsgpu_assign_seeds_batch(lcsgpu_ctx* ctx, const int32_t* seed_ids, const in
 // then ONE workgroup per sample runs that sample's whole chain of local searches (clarans_chain_kernel); the host only
 // pre-draws the step positions and composes the shuffles (neither generator looks at a search, Clustering.cpp:43-46) --
 // both depend on the shape (members, medoids) alone, so samples of one shape share them.
-int lcsgpu_clarans_batch(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* offsets, int32_t n_jobs, int distance_kind,
-                         const int32_t* n_medoids, int32_t n_fixed, float explore_fraction, int32_t num_local, int32_t* medoids_out)
+// The body of lcsgpu_clarans_batch and lcsgpu_clarans_large_batch.  allow_large: samples beyond the chain kernel's shapes
+// (CLARANS_MAX_*) are not refused but run in clarans_large_chain_kernel, up to CLARANS_LARGE_MAX_MEMBERS members; the
+// samples inside those shapes run through the chain kernel either way.
+static int clarans_batch_impl(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* offsets, int32_t n_jobs, int distance_kind,
+                              const int32_t* n_medoids, int32_t n_fixed, float explore_fraction, int32_t num_local, int32_t* medoids_out,
+                              bool allow_large)
 {
     if (!ctx) return fail(LCSGPU_E_INVALID, "NULL ctx");
     if (ctx->n < 0) return fail(LCSGPU_E_STATE, "no sequence set uploaded");
@@ -566,7 +570,11 @@ int lcsgpu_clarans_batch(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* off
         if (n < 1 || n > 0x7fffffff) return fail(LCSGPU_E_INVALID, "bad sample %d", j);
         if (k < 1 || k > n || n_fixed >= k)
             return fail(LCSGPU_E_INVALID, "bad CLARANS shape: %d medoids (%d fixed) of %lld, %d searches", k, n_fixed, (long long)n, num_local);
-        if (k > lcsgpu::CLARANS_MAX_MEDOIDS || n - k > lcsgpu::CLARANS_MAX_NONMEDOIDS)
+        if (allow_large) {
+            if (n > lcsgpu::CLARANS_LARGE_MAX_MEMBERS)
+                return fail(LCSGPU_E_UNSUPPORTED, "device CLARANS handles at most %d sample members (asked: %lld)", lcsgpu::CLARANS_LARGE_MAX_MEMBERS,
+                            (long long)n);
+        } else if (k > lcsgpu::CLARANS_MAX_MEDOIDS || n - k > lcsgpu::CLARANS_MAX_NONMEDOIDS)
             return fail(LCSGPU_E_UNSUPPORTED, "device CLARANS handles at most %d medoids and %d other sample members (asked: %d, %lld)",
                         lcsgpu::CLARANS_MAX_MEDOIDS, lcsgpu::CLARANS_MAX_NONMEDOIDS, k, (long long)(n - k));
         med_off[j + 1] = med_off[j] + k;
@@ -669,35 +677,40 @@ int lcsgpu_clarans_batch(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* off
     const size_t o_states = at; at += a256((size_t)n_live * lcsgpu::CLARANS_STATE_WORDS * 4);
     const size_t o_ids = at; at += a256((size_t)n_total * 4);
     const size_t o_best = at; at += a256((size_t)med_off[n_jobs] * 4);
-    struct Place { char* D; char* DM; char* cand; char* st; char* log; };
+    struct Place { char* D; char* DM; char* cand; char* st; char* log; char* dn; };
+    auto is_large = [&](int32_t j) { // beyond the chain kernel's registers: clarans_large_chain_kernel
+        const int64_t n = offsets[j + 1] - offsets[j];
+        return n_medoids[j] > lcsgpu::CLARANS_MAX_MEDOIDS || n - n_medoids[j] > lcsgpu::CLARANS_MAX_NONMEDOIDS;
+    };
     std::vector<Place> place((size_t)n_live);
     int max_n = 0, max_k = 0;
     size_t sample_bytes = 0;
     {   // every sample's work area out of the context's chunks (this call owns them: it holds the FRONT lane); what the chunks
         // there are cannot hold comes out of ONE new chunk
-        auto area = [&](int q, size_t* o_DM, size_t* o_cand, size_t* o_st, size_t* o_log) {
+        auto area = [&](int q, size_t* o_DM, size_t* o_cand, size_t* o_st, size_t* o_log, size_t* o_dn) {
             const int32_t j = live[(size_t)q];
             const size_t n = (size_t)(offsets[j + 1] - offsets[j]), k = (size_t)n_medoids[j];
             *o_DM = a256(n * n * 4);
             *o_cand = *o_DM + a256(n * k * 4);
             *o_st = *o_cand + a256(n * 4);
             *o_log = *o_st + a256(n * 16);
-            return *o_log + a256((n + 1) * 4);
+            *o_dn = *o_log + a256((n + 1) * 4);
+            return *o_dn + (is_large(j) ? a256(n * 4) : 0);
         };
         size_t chunk = 0, used = 0; // the chunk being filled
         for (int q = 0; q < n_live; ++q) {
             const int32_t j = live[(size_t)q];
             const size_t n = (size_t)(offsets[j + 1] - offsets[j]), k = (size_t)n_medoids[j];
-            size_t o_DM, o_cand, o_st, o_log;
-            const size_t o_D = 0, need = area(q, &o_DM, &o_cand, &o_st, &o_log);
+            size_t o_DM, o_cand, o_st, o_log, o_dn;
+            const size_t o_D = 0, need = area(q, &o_DM, &o_cand, &o_st, &o_log, &o_dn);
             while (chunk < ctx->sample_chunks.size() && ctx->sample_chunks[chunk].cap - used < need) {
                 ++chunk;
                 used = 0;
             }
             if (chunk == ctx->sample_chunks.size()) {
                 ctx->sample_chunks.emplace_back();
-                size_t rest = 0, a, b, c, d;
-                for (int r = q; r < n_live; ++r) rest += area(r, &a, &b, &c, &d);
+                size_t rest = 0, a, b, c, d, e;
+                for (int r = q; r < n_live; ++r) rest += area(r, &a, &b, &c, &d, &e);
                 rc = reserve_big(ctx, ctx->sample_chunks.back(), rest, "CLARANS samples");
                 if (rc) {
                     ctx->sample_chunks.pop_back();
@@ -706,11 +719,11 @@ int lcsgpu_clarans_batch(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* off
                 used = 0;
             }
             char* b = (char*)ctx->sample_chunks[chunk].p + used;
-            place[(size_t)q] = Place{b + o_D, b + o_DM, b + o_cand, b + o_st, b + o_log};
+            place[(size_t)q] = Place{b + o_D, b + o_DM, b + o_cand, b + o_st, b + o_log, b + o_dn};
             used += need;
             sample_bytes += need;
             max_n = std::max(max_n, (int)n);
-            max_k = std::max(max_k, (int)k);
+            if (!is_large(j)) max_k = std::max(max_k, (int)k); // (the chain kernel's instantiation: by its own chains)
         }
     }
     rc = reserve_big(ctx, L.d_work, at, "CLARANS batch tables");
@@ -723,6 +736,9 @@ int lcsgpu_clarans_batch(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* off
     lcsgpu::ClaransChain* h_chains = (lcsgpu::ClaransChain*)L.h_small.p;
     int32_t* h_states = (int32_t*)((char*)L.h_small.p + a256((size_t)n_live * sizeof(lcsgpu::ClaransChain)));
     static const int draws_first = std::max(16, tune_int("clarans_draws", 65536)), slice_us = std::max(0, tune_int("clarans_slice_us", 0));
+    // a launch of clarans_large_chain_kernel ends after that long and its chains go on in the next (0 = no limit): such a chain
+    // can run for seconds, and no launch should
+    static const int large_slice_us = std::max(0, tune_int("clarans_large_slice_us", 250000));
     for (auto& shp : shapes) {
         Shape& sh = *shp;
         if (sh.n == sh.k) continue;
@@ -774,6 +790,7 @@ int lcsgpu_clarans_batch(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* off
         c.best = (int32_t*)(base + o_best) + med_off[j];
         c.tri0 = tri_base[(size_t)j];
         c.num_local = num_local;
+        c.dn_member = is_large(j) ? (float*)p.dn : nullptr;
         int32_t* st = h_states + (size_t)q * lcsgpu::CLARANS_STATE_WORDS;
         st[4] = 1;  // ST_FRESH
         st[10] = 1; // ST_FIRST
@@ -793,14 +810,24 @@ int lcsgpu_clarans_batch(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* off
     lap(0, false);
     // the chains: normally one launch; a chain that runs out of positions (or, under LCSGPU_TUNE clarans_slice_us, of time)
     // comes back for another
-    std::vector<int> todo((size_t)n_live);
-    for (int q = 0; q < n_live; ++q) todo[(size_t)q] = q;
+    std::vector<int> todo;
+    todo.reserve((size_t)n_live);
+    int n_large = 0;
+    for (int q = 0; q < n_live; ++q)
+        if (!is_large(live[(size_t)q])) todo.push_back(q);
+    for (int q = 0; q < n_live; ++q)
+        if (is_large(live[(size_t)q])) {
+            todo.push_back(q);
+            ++n_large;
+        }
     std::vector<lcsgpu::ClaransChain> all(h_chains, h_chains + n_live);
-    int launches = 0;
+    int launches = 0, large_launches = 0;
     long accepts = 0, steps = 0;
     std::vector<int32_t> ticks, where;
     while (!todo.empty()) {
         const int nt = (int)todo.size();
+        int nt_small = 0; // (todo keeps its order: the chain kernel's chains first)
+        while (nt_small < nt && !is_large(live[(size_t)todo[(size_t)nt_small]])) ++nt_small;
         for (int t = 0; t < nt; ++t) {
             lcsgpu::ClaransChain& c = h_chains[t];
             c = all[(size_t)todo[(size_t)t]];
@@ -809,13 +836,18 @@ int lcsgpu_clarans_batch(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* off
             c.a.draws_len = (int32_t)sh.draws.size();
         }
         HIP_TRY(hipMemcpyAsync(base + o_chains, h_chains, (size_t)nt * sizeof(lcsgpu::ClaransChain), hipMemcpyHostToDevice, L.stream));
-        HIP_TRY(lcsgpu::launch_clarans_chains((const lcsgpu::ClaransChain*)(base + o_chains), nt, max_k, slice_us, L.stream));
+        HIP_TRY(lcsgpu::launch_clarans_chains((const lcsgpu::ClaransChain*)(base + o_chains), nt_small, max_k, slice_us, L.stream));
+        HIP_TRY(lcsgpu::launch_clarans_large_chains((const lcsgpu::ClaransChain*)(base + o_chains) + nt_small, nt - nt_small, large_slice_us, L.stream));
+        large_launches += nt > nt_small;
         HIP_TRY(hipMemcpyAsync(h_states, base + o_states, (size_t)n_live * lcsgpu::CLARANS_STATE_WORDS * 4, hipMemcpyDeviceToHost, L.stream));
         HIP_TRY(hipEventRecord(L.ev_done, L.stream));
         HIP_TRY(hipEventSynchronize(L.ev_done));
         L.plan_in_flight = false;
         ++launches;
         std::vector<int> again;
+        // more pre-drawn positions: ONE target per shape and round, however many of its chains ran out -- twice what the
+        // shape had when the round began, or what the chain that is furthest asks for
+        std::vector<size_t> want(shapes.size(), 0);
         for (int q : todo) {
             const int32_t* st = h_states + (size_t)q * lcsgpu::CLARANS_STATE_WORDS;
             if (st[1]) { // ST_DONE: the whole chain
@@ -827,11 +859,16 @@ int lcsgpu_clarans_batch(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* off
             }
             again.push_back(q);
             if (st[7]) { // ST_MORE_DRAWS
-                Shape& sh = *shapes[(size_t)shape_of[(size_t)live[(size_t)q]]];
-                rc = extend_draws(sh, std::max(sh.draws.size() * 2, (size_t)st[0] + (size_t)st[8] + (size_t)draws_first));
-                if (rc) return rc;
+                const size_t si = (size_t)shape_of[(size_t)live[(size_t)q]];
+                want[si] = std::max(want[si], std::max(shapes[si]->draws.size() * 2, (size_t)st[0] + (size_t)st[8] + (size_t)draws_first));
             }
         }
+        for (size_t si = 0; si < shapes.size(); ++si)
+            if (want[si]) {
+                if (want[si] > 0x7fffffffu) return fail(LCSGPU_E_UNSUPPORTED, "a CLARANS chain needs more than 2^31 step positions");
+                rc = extend_draws(*shapes[si], want[si]);
+                if (rc) return rc;
+            }
         todo.swap(again);
         if (launches > 100000) return fail(LCSGPU_E_STATE, "CLARANS batch does not finish");
     }
@@ -862,10 +899,36 @@ int lcsgpu_clarans_batch(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* off
     if (profile)
         fprintf(stderr, "clarans.batch parts: gate %.1f ms, planning the triangles %.1f, their kernels %.1f, work area (%.2f GB) %.1f, tables + distances %.1f, chains + results %.1f\n",
                 1e3 * t_prof[0], 1e3 * t_prof[1], 1e3 * t_prof[2], at / 1e9, 1e3 * t_prof[3], 1e3 * t_prof[4], 1e3 * t_prof[5]);
+    if (getenv("LCSGPU_PROFILE") && n_large)
+        fprintf(stderr, "clarans.large: %d chain(s) beyond the chain kernel's shapes, %d launch(es) of at most %d us\n", n_large, large_launches, large_slice_us);
     if (getenv("LCSGPU_PROFILE"))
         fprintf(stderr, "clarans.batch: %d samples (%d searched, %zu shapes), %d launch(es), %ld accepts, %ld steps looked at, %.3f s\n", n_jobs, n_live,
                 shapes.size(), launches, accepts, steps, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_call).count());
     return LCSGPU_OK;
+}
+
+// the C-ABI's boundary: no exception leaves it (a std::bad_alloc of the host-side tables would end in std::terminate)
+static int clarans_batch_guarded(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* offsets, int32_t n_jobs, int distance_kind,
+                                 const int32_t* n_medoids, int32_t n_fixed, float explore_fraction, int32_t num_local, int32_t* medoids_out,
+                                 bool allow_large)
+{
+    try {
+        return clarans_batch_impl(ctx, ids, offsets, n_jobs, distance_kind, n_medoids, n_fixed, explore_fraction, num_local, medoids_out, allow_large);
+    } catch (const std::exception& e) {
+        return fail(LCSGPU_E_NOMEM, "CLARANS batch: %s", e.what());
+    }
+}
+
+int lcsgpu_clarans_batch(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* offsets, int32_t n_jobs, int distance_kind,
+                         const int32_t* n_medoids, int32_t n_fixed, float explore_fraction, int32_t num_local, int32_t* medoids_out)
+{
+    return clarans_batch_guarded(ctx, ids, offsets, n_jobs, distance_kind, n_medoids, n_fixed, explore_fraction, num_local, medoids_out, false);
+}
+
+int lcsgpu_clarans_large_batch(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* offsets, int32_t n_jobs, int distance_kind,
+                               const int32_t* n_medoids, int32_t n_fixed, float explore_fraction, int32_t num_local, int32_t* medoids_out)
+{
+    return clarans_batch_guarded(ctx, ids, offsets, n_jobs, distance_kind, n_medoids, n_fixed, explore_fraction, num_local, medoids_out, true);
 }
 
 int lcsgpu_clarans(lcsgpu_ctx* ctx, const int32_t* ids, int32_t n_ids, int distance_kind, int32_t n_medoids,
@@ -873,7 +936,15 @@ int lcsgpu_clarans(lcsgpu_ctx* ctx, const int32_t* ids, int32_t n_ids, int dista
 {
     if (!ids || !medoids_out || n_ids < 1) return fail(LCSGPU_E_INVALID, "bad sample / output");
     const int64_t offsets[2] = {0, n_ids};
-    return lcsgpu_clarans_batch(ctx, ids, offsets, 1, distance_kind, &n_medoids, n_fixed, explore_fraction, num_local, medoids_out);
+    return clarans_batch_guarded(ctx, ids, offsets, 1, distance_kind, &n_medoids, n_fixed, explore_fraction, num_local, medoids_out, false);
+}
+
+int lcsgpu_clarans_large(lcsgpu_ctx* ctx, const int32_t* ids, int32_t n_ids, int distance_kind, int32_t n_medoids,
+                         int32_t n_fixed, float explore_fraction, int32_t num_local, int32_t* medoids_out)
+{
+    if (!ids || !medoids_out || n_ids < 1) return fail(LCSGPU_E_INVALID, "bad sample / output");
+    const int64_t offsets[2] = {0, n_ids};
+    return clarans_batch_guarded(ctx, ids, offsets, 1, distance_kind, &n_medoids, n_fixed, explore_fraction, num_local, medoids_out, true);
 }
 
 } // extern "C"

@@ -30,7 +30,8 @@ namespace lcsgpu_impl {
 // thread-local error text of lcsgpu_last_error(); returns `code`
 int fail(int code, const char* fmt, ...);
 // numeric tuning knobs, LCSGPU_TUNE="key=value,key=value" (no alternate code paths behind them): clarans_slice_us (a launch of
-// search chains ends after that long and the chains continue in the next: 0 = none, a test aid), clarans_draws (step positions
+// search chains ends after that long and the chains continue in the next: 0 = none, a test aid), clarans_large_slice_us (the same
+// for the chains of clarans_large_chain_kernel, where it is on by default: 250000), clarans_draws (step positions
 // drawn for a sample shape before its first launch, 65536), assign_batch_kb (LCS rectangles of one launch of the batched seed
 // assignment, 2 GB), upgma_spare (spare slots of the UPGMA matrix, n / 10)
 int tune_int(const char* key, int dflt);

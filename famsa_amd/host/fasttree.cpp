@@ -186,7 +186,7 @@ void partial_shuffle(int* first, int* middle, int* last, Gen& g)
 }
 
 // ---- CLARANS k-medoids on the host: the form the device search has (csrc/clarans_kernels.hip), run serially -----------
-// Used where there is no device search: a matrix source without a GPU (the CPU suite), more than 1024 medoids, or on
+// Used where there is no device search: a matrix source without a GPU (the CPU suite), a sample of more than 32768 members, or on
 // request (FAMSA_CLARANS_HOST=1, the checker of the device search).  What it must reproduce is CLARANS::operator()
 // (reference tree/Clustering.cpp:17-305): the same draws, the same float additions in the same order, the same
 // comparison directions -- the sign of a delta decides the search.  How it is organised is this engine's own, and the

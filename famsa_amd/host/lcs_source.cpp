@@ -385,14 +385,15 @@ bool GpuLcsSource::clarans(const int* ids, int n_ids, int distance_kind, int n_m
     if (host_test("clarans_host")) return false; // the checker of the device search: keep it on the host
     const double t0 = now_s();
     lcsgpu_ctx* c = pick();
-    const int rc = lcsgpu_clarans(c, ids, n_ids, distance_kind, n_medoids, n_fixed, explore_fraction, num_local, medoids);
+    // (any shape up to the engine's cap of 32768 members; a sample inside the chain kernel's shapes runs as in lcsgpu_clarans)
+    const int rc = lcsgpu_clarans_large(c, ids, n_ids, distance_kind, n_medoids, n_fixed, explore_fraction, num_local, medoids);
     if (rc == LCSGPU_E_UNSUPPORTED) {
         static std::atomic<bool> told{false};
         if (profile_on() && !told.exchange(true))
             fprintf(stderr, "[famsa-gpu] %s -- such samples are searched on the host (one thread each)\n", lcsgpu_last_error());
         return false;
     }
-    check(rc, "lcsgpu_clarans");
+    check(rc, "lcsgpu_clarans_large");
     note(st_clarans_, now_s() - t0, (double)n_ids * (n_ids - 1) / 2);
     add_kernel_ms(c);
     return true;
@@ -449,8 +450,8 @@ bool GpuLcsSource::clarans_batch(const int* ids, const int64_t* offsets, int n_j
     over_contexts(n_jobs, weight, [&](int d, int j0, int j1) {
         std::vector<int64_t> off((size_t)(j1 - j0) + 1);
         for (int j = j0; j <= j1; ++j) off[(size_t)(j - j0)] = offsets[j] - offsets[j0];
-        const int rc = lcsgpu_clarans_batch(ctxs_[(size_t)d], ids + offsets[j0], off.data(), j1 - j0, distance_kind, n_medoids + j0, n_fixed,
-                                            explore_fraction, num_local, medoids_out + med_off[(size_t)j0]);
+        const int rc = lcsgpu_clarans_large_batch(ctxs_[(size_t)d], ids + offsets[j0], off.data(), j1 - j0, distance_kind, n_medoids + j0, n_fixed,
+                                                  explore_fraction, num_local, medoids_out + med_off[(size_t)j0]);
         if (rc == LCSGPU_E_UNSUPPORTED) {
             unsupported = true;
             static std::atomic<bool> told{false};
@@ -458,7 +459,7 @@ bool GpuLcsSource::clarans_batch(const int* ids, const int64_t* offsets, int n_j
                 fprintf(stderr, "[famsa-gpu] %s -- such samples are searched on the host (one thread each)\n", lcsgpu_last_error());
             return;
         }
-        check(rc, "lcsgpu_clarans_batch");
+        check(rc, "lcsgpu_clarans_large_batch");
         add_kernel_ms(ctxs_[(size_t)d]);
     });
     if (unsupported) return false;

@@ -74,6 +74,8 @@ def load_library():
         "lcsgpu_assign_seeds": (C.c_int, [vp, pi32, i32, pi32, i32, C.c_int, i32, vp, vp]),
         "lcsgpu_clarans": (C.c_int, [vp, pi32, i32, C.c_int, i32, i32, C.c_float, i32, pi32]),
         "lcsgpu_clarans_batch": (C.c_int, [vp, pi32, C.POINTER(C.c_int64), i32, C.c_int, pi32, i32, C.c_float, i32, pi32]),
+        "lcsgpu_clarans_large": (C.c_int, [vp, pi32, i32, C.c_int, i32, i32, C.c_float, i32, pi32]),
+        "lcsgpu_clarans_large_batch": (C.c_int, [vp, pi32, C.POINTER(C.c_int64), i32, C.c_int, pi32, i32, C.c_float, i32, pi32]),
         "lcsgpu_assign_seeds_batch": (C.c_int, [vp, pi32, C.POINTER(C.c_int64), pi32, C.POINTER(C.c_int64), i32, C.c_int, vp, vp]),
         "lcsgpu_dist_text_begin": (C.c_int, [vp, C.c_char_p, vp, C.c_int, C.c_int, i32]),
         "lcsgpu_dist_text_submit": (C.c_int, [vp, i32, i32, i32]),
@@ -317,15 +319,23 @@ class LcsGpu:
         self._check(self._lib.lcsgpu_assign_seeds(self._ctx, s_ptr, len(s_arr), c_ptr, len(c_arr), kind, first_k,
                                                   dist.ctypes.data, assign.ctypes.data))
 
-    def clarans(self, ids, n_medoids, n_fixed=1, explore_fraction=0.1, num_local=2, kind=1):
+    def clarans(self, ids, n_medoids, n_fixed=1, explore_fraction=0.1, num_local=2, kind=1, _call="lcsgpu_clarans"):
         """CLARANS medoids (member numbers within `ids`) of the sample `ids`, computed on the device."""
         arr, ptr = _ids(ids)
         out = np.zeros(max(n_medoids, 1), dtype=np.int32)
-        self._check(self._lib.lcsgpu_clarans(self._ctx, ptr, len(arr), kind, n_medoids, n_fixed, explore_fraction,
-                                             num_local, out.ctypes.data_as(C.POINTER(C.c_int32))))
+        self._check(getattr(self._lib, _call)(self._ctx, ptr, len(arr), kind, n_medoids, n_fixed, explore_fraction,
+                                              num_local, out.ctypes.data_as(C.POINTER(C.c_int32))))
         return out[:n_medoids]
 
-    def clarans_batch(self, samples, n_medoids, n_fixed=1, explore_fraction=0.1, num_local=2, kind=1):
+    def clarans_large(self, ids, n_medoids, n_fixed=1, explore_fraction=0.1, num_local=2, kind=1):
+        """lcsgpu_clarans_large: `clarans` for a sample of any shape up to 32768 members."""
+        return self.clarans(ids, n_medoids, n_fixed, explore_fraction, num_local, kind, _call="lcsgpu_clarans_large")
+
+    def clarans_large_batch(self, samples, n_medoids, n_fixed=1, explore_fraction=0.1, num_local=2, kind=1):
+        """lcsgpu_clarans_large_batch: `clarans_batch` for samples of any shapes up to 32768 members."""
+        return self.clarans_batch(samples, n_medoids, n_fixed, explore_fraction, num_local, kind, _call="lcsgpu_clarans_large_batch")
+
+    def clarans_batch(self, samples, n_medoids, n_fixed=1, explore_fraction=0.1, num_local=2, kind=1, _call="lcsgpu_clarans_batch"):
         """lcsgpu_clarans_batch: `samples` = list of id arrays, `n_medoids` = one count or a list; returns a list of arrays."""
         ks = np.ascontiguousarray([n_medoids] * len(samples) if np.isscalar(n_medoids) else n_medoids, dtype=np.int32)
         off = np.zeros(len(samples) + 1, dtype=np.int64)
@@ -333,8 +343,8 @@ class LcsGpu:
         ids = np.ascontiguousarray(np.concatenate([np.asarray(s, np.int32) for s in samples]) if samples else np.zeros(0, np.int32), dtype=np.int32)
         out = np.zeros(max(int(ks.sum()), 1), dtype=np.int32)
         p32 = C.POINTER(C.c_int32)
-        self._check(self._lib.lcsgpu_clarans_batch(self._ctx, ids.ctypes.data_as(p32), off.ctypes.data_as(C.POINTER(C.c_int64)), len(samples), kind,
-                                                   ks.ctypes.data_as(p32), n_fixed, explore_fraction, num_local, out.ctypes.data_as(p32)))
+        self._check(getattr(self._lib, _call)(self._ctx, ids.ctypes.data_as(p32), off.ctypes.data_as(C.POINTER(C.c_int64)), len(samples), kind,
+                                              ks.ctypes.data_as(p32), n_fixed, explore_fraction, num_local, out.ctypes.data_as(p32)))
         cuts = np.concatenate([[0], np.cumsum(ks)])
         return [out[cuts[i]:cuts[i + 1]].copy() for i in range(len(samples))]
 

@@ -429,6 +429,20 @@ int lcsgpu_clarans_batch(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* off
 int lcsgpu_assign_seeds_batch(lcsgpu_ctx* ctx, const int32_t* seed_ids, const int64_t* seed_offsets, const int32_t* col_ids,
                               const int64_t* col_offsets, int32_t n_jobs, int distance_kind, float* dist, int32_t* assign);
 
+/* lcsgpu_clarans / lcsgpu_clarans_batch for samples of ANY shape up to 32768 members: the same arguments, the same
+ * medoids (the reference's).  A sample inside the shapes of lcsgpu_clarans (at most 1024 medoids and 2048 other members)
+ * runs exactly as it does there; the others run in a second kernel that keeps the positions' state in memory and walks
+ * it in slices -- still one workgroup per sample, in launches of bounded length (LCSGPU_TUNE clarans_large_slice_us,
+ * default 250000; the chains go on in the next launch where they stood).  Any mix of shapes in one call; all triangles
+ * and all float matrices still come from one batched launch each.  The float matrix of a sample takes 4 n^2 bytes of
+ * device memory (4.3 GB at the cap): LCSGPU_E_NOMEM if that cannot be had.
+ * LCSGPU_E_UNSUPPORTED (nothing computed) only for a sample of more than 32768 members: the caller's host search. */
+int lcsgpu_clarans_large(lcsgpu_ctx* ctx, const int32_t* ids, int32_t n_ids, int distance_kind, int32_t n_medoids,
+                         int32_t n_fixed, float explore_fraction, int32_t num_local, int32_t* medoids_out);
+int lcsgpu_clarans_large_batch(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* offsets, int32_t n_jobs, int distance_kind,
+                               const int32_t* n_medoids, int32_t n_fixed, float explore_fraction, int32_t num_local,
+                               int32_t* medoids_out);
+
 /* Block until everything queued on the context's stream has finished. */
 int lcsgpu_sync(lcsgpu_ctx* ctx);
 

@@ -350,12 +350,14 @@ __device__ __forceinline__ bool fuse_tile_is_useless(const RowsArgs& a, const ld
         cd = d2 > cd ? d2 : cd;
     }
     const int wave = tid >> 6;
+    const bool any_has = __builtin_amdgcn_ballot_w64(has) != 0; // some column of this wave has a pair in the tile
     if ((tid & 63) == 0) {
         red[wave * 8 + 0] = cmin;
         red[wave * 8 + 1] = cmax;
         red[wave * 8 + 2] = copen;
         red[wave * 8 + 3] = (uint32_t)cd;
         red[wave * 8 + 4] = (uint32_t)(cd >> 32);
+        red[wave * 8 + 5] = any_has ? 1u : 0u;
     }
     // the rows (at most 32: the first wave's lanes), every wave's view of a row folded
     lmin = 0xffffffffu; lmax = 0u; open = 0u; dmax = 0ull;
@@ -378,9 +380,10 @@ __device__ __forceinline__ bool fuse_tile_is_useless(const RowsArgs& a, const ld
     }
     __syncthreads();
     if (tid == 0) {
-        uint32_t kmin = 0xffffffffu, kmax = 0u, kopen = 0u;
+        uint32_t kmin = 0xffffffffu, kmax = 0u, kopen = 0u, kany = 0u;
         unsigned long long kd = 0ull;
         for (int w = 0; w < 4; ++w) {
+            kany |= red[w * 8 + 5];
             kmin = red[w * 8 + 0] < kmin ? red[w * 8 + 0] : kmin;
             kmax = red[w * 8 + 1] > kmax ? red[w * 8 + 1] : kmax;
             kopen |= red[w * 8 + 2];
@@ -388,7 +391,9 @@ __device__ __forceinline__ bool fuse_tile_is_useless(const RowsArgs& a, const ld
             kd = d > kd ? d : kd;
         }
         bool useless = false;
-        if (kmax == 0u) useless = true; // no pair at all in this tile
+        // (kmax == 0 does not say so: the columns that have a pair may all be 0 long, and such pairs -- the largest
+        // finite distance but one, settled by the ids -- are some vertices' only edges)
+        if (!kany) useless = true; // no pair at all in this tile
         else if (!kopen && !open && lmax != 0u) {
             // rows [lmin, lmax], columns [kmin, kmax]
             const uint32_t gap = kmin > lmax ? kmin - lmax : (lmin > kmax ? lmin - kmax : 0u);

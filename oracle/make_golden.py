@@ -152,6 +152,19 @@ def main():
     meta["synth2k"] = {"triangle_u16_sha256": sha(tri), "codes_sha256": sha(codes)}
     ref.close(h)
 
+    # 5. a whole 256-id block of empty sequences behind 256 real ones (tests/mst_shapes.py "zero_last", gap-only records):
+    #    famsa -keep-duplicates -gt sl | slink -gt_export
+    import mst_shapes
+    mst_shapes.write_zero_last_fasta("/tmp/zero_last.fasta")
+    h = ref.open_fasta("/tmp/zero_last.fasta")
+    meta["zero_last"] = {"n": ref.lib.ref_count(h), "call": "ref_open_fasta + ref_tree_newick(gt, distance=1, keep_dups=1, threads=4, isa=2)",
+                         "fasta_sha256": hashlib.sha256(open("/tmp/zero_last.fasta", "rb").read()).hexdigest()}
+    for gt in ("sl", "slink"):
+        t = ref.tree(h, gt, keep_dups=1)
+        open(os.path.join(G, f"zero_last_{gt}.dnd"), "wb").write(t)
+        meta["zero_last"][f"{gt}_newick_sha256"] = hashlib.sha256(t).hexdigest()
+    ref.close(h)
+
     json.dump(meta, open(os.path.join(G, "meta.json"), "w"), indent=1, sort_keys=True)
     print(json.dumps(meta, indent=1))
 

@@ -41,4 +41,27 @@ hipError_t launch_clarans_chains(const ClaransChain* chains, int n_chains, int m
 // the same for chains of any shape up to CLARANS_LARGE_MAX_MEMBERS (state in memory, walked in slices)
 hipError_t launch_clarans_large_chains(const ClaransChain* chains, int n_chains, int slice_us, hipStream_t stream);
 
+// ---- Prim's MST of many small groups in one launch: one workgroup per group (mst_kernels.hip) ----
+constexpr int MST_GROUP_MAX_MEMBERS = 4096; // = LCSGPU_MST_BATCH_MAX_MEMBERS: a group's per-vertex state sits in one workgroup's LDS
+struct GroupPrimJob {
+    int64_t tri0;  // element offset of the group's packed LCS triangle in the launch's triangle buffer
+    int64_t sq0;   // ... of its m x m square in the square buffer (square layout only)
+    int64_t edge0; // record offset of its m - 1 edges
+    int32_t id0;   // position of its first member in the concatenated id list
+    int32_t m;     // members, 2 .. MST_GROUP_MAX_MEMBERS
+};
+struct GroupPrimArgs {
+    const uint16_t* tri;      // the groups' packed triangles (ref = the later member)
+    uint16_t* sq;             // NULL = read the triangles as they are; else the scratch the squares are expanded into
+    const GroupPrimJob* jobs; // longest first
+    const int64_t* row0;      // [n_jobs + 1] prefix sums of m over the jobs (the expansion's grid); square layout only
+    const int32_t* ids;       // the concatenated id lists
+    const uint32_t* lens;
+    const double* pow_table;  // pow(i, 0.75), i < pow_n, from the host's libm
+    MstEdge* edges;
+    int64_t total_rows;       // row0[n_jobs]
+    int32_t pow_n, n_jobs, kind, max_m;
+};
+hipError_t launch_group_prim(const GroupPrimArgs& a, hipStream_t stream);
+
 } // namespace lcsgpu

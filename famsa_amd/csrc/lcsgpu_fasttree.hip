@@ -278,6 +278,136 @@ int lcsgpu_lcs_triangles_batch(lcsgpu_ctx* ctx, const int32_t* ids, const int64_
     return LCSGPU_OK;
 }
 
+// Prim's MST of many id lists: the lists' triangles by the launches of lcsgpu_lcs_triangles_batch, then ONE launch with a
+// workgroup per list (mst_kernels.hip, mst_group_prim_kernel), longest lists first.
+static int mst_prim_batch_impl(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* group_offsets, int32_t n_groups, int distance_kind,
+                               lcsgpu_mst_edge* out_edges)
+{
+    const bool triangle_orientation = (distance_kind & LCSGPU_MST_TRIANGLE_ORIENTATION) != 0;
+    distance_kind &= ~LCSGPU_MST_TRIANGLE_ORIENTATION;
+    if (!ctx) return fail(LCSGPU_E_INVALID, "NULL ctx");
+    if (ctx->n < 0) return fail(LCSGPU_E_STATE, "no sequence set uploaded");
+    if (distance_kind != LCSGPU_DIST_INDEL_DIV_LCS && distance_kind != LCSGPU_DIST_INDEL075_DIV_LCS)
+        return fail(LCSGPU_E_INVALID, "unknown distance kind %d", distance_kind);
+    if (n_groups < 0 || (n_groups > 0 && !group_offsets)) return fail(LCSGPU_E_INVALID, "bad group table");
+    if (n_groups == 0) return LCSGPU_OK;
+    if (group_offsets[0] != 0) return fail(LCSGPU_E_INVALID, "group_offsets[0] must be 0");
+    const int64_t n_total = group_offsets[n_groups];
+    if (n_total < 0 || n_total > 0x7fffffff) return fail(LCSGPU_E_INVALID, "bad total id count");
+    if (n_total > 0 && !ids) return fail(LCSGPU_E_INVALID, "NULL ids");
+    // everything that refuses comes first: nothing is computed, out_edges stays as it is
+    std::vector<lcsgpu::GroupPrimJob> jobs;
+    int64_t n_edges = 0, sq_elems = 0;
+    for (int32_t g = 0; g < n_groups; ++g) {
+        const int64_t m = group_offsets[g + 1] - group_offsets[g];
+        if (m < 0) return fail(LCSGPU_E_INVALID, "group_offsets not ascending");
+        if (m > LCSGPU_MST_BATCH_MAX_MEMBERS)
+            return fail(LCSGPU_E_UNSUPPORTED, "group %d has %lld members: the batched MST handles at most %d (use lcsgpu_mst_prim)", g,
+                        (long long)m, LCSGPU_MST_BATCH_MAX_MEMBERS);
+        if (m >= 2) {
+            jobs.push_back(lcsgpu::GroupPrimJob{(int64_t)g /* the group, until its triangle's place is known */, 0, n_edges, (int32_t)group_offsets[g], (int32_t)m});
+            n_edges += m - 1;
+        }
+    }
+    for (int64_t p = 0; p < n_total; ++p) {
+        const int32_t id = ids[p];
+        if (id < 0 || id >= ctx->n) return fail(LCSGPU_E_INVALID, "id %d out of range", id);
+        if (ctx->lens[(size_t)id] > 65535)
+            return fail(LCSGPU_E_UNSUPPORTED, "sequence %d is longer than 65535 residues: the batched MST keeps 16-bit LCS values", id);
+        if (!triangle_orientation && ctx->quirk[(size_t)id])
+            return fail(LCSGPU_E_UNSUPPORTED, "sequence %d is orientation sensitive: MSTPrim's distances depend on which endpoint is "
+                                              "the ref, the triangle does not hold them (use lcsgpu_mst_prim)", id);
+    }
+    if (jobs.empty()) return LCSGPU_OK;
+    if (!out_edges) return fail(LCSGPU_E_INVALID, "NULL out_edges");
+    // The LCS values of (cur, v) from the group's expanded m x m square (one contiguous row per step) or -- LCSGPU_TUNE
+    // mst_batch_square=0 -- from the packed triangle as it is (v > cur: a strided 2-byte gather).  A step is latency more
+    // than bytes, so the square gains little: the Prim launch with its expansion 0.378 against 0.385 ms at m = 256, 1.95
+    // against 2.08 ms at 1000, 17.6 against 19.3 ms at 4096 (profiles/batch_trees.txt) -- faster at every size from 200 up,
+    // for twice the triangles' memory again.
+    static const int use_square = tune_int("mst_batch_square", 1);
+
+    LaneGuard guard(ctx, LaneGuard::ANY);
+    Lane& L = guard.lane();
+    std::vector<int64_t> tri_base;
+    int64_t count = 0;
+    bool had_long = false;
+    struct Shared { // from the first launch until the kernels have run (lcsgpu_lcs_triangles_batch)
+        ComputeGate& g;
+        bool held = false;
+        ~Shared() { if (held) g.unlock_shared(); }
+    } hold{ctx->gate};
+    int rc = batch_triangles_to_device(ctx, L, ids, group_offsets, n_groups, 2, tri_base, &count, &had_long, [&] {
+        hold.g.lock_shared();
+        hold.held = true;
+    });
+    if (rc) return rc;
+    if (count <= 0) return fail(LCSGPU_E_STATE, "the batched MST found no pair to compute");
+    // longest first: the groups that take the most steps start first
+    std::stable_sort(jobs.begin(), jobs.end(), [](const lcsgpu::GroupPrimJob& x, const lcsgpu::GroupPrimJob& y) { return x.m > y.m; });
+    std::vector<int64_t> row0(jobs.size() + 1, 0);
+    int32_t max_m = 0;
+    for (size_t j = 0; j < jobs.size(); ++j) {
+        lcsgpu::GroupPrimJob& job = jobs[j];
+        job.tri0 = tri_base[(size_t)job.tri0];
+        job.sq0 = sq_elems;
+        sq_elems += (int64_t)job.m * job.m;
+        row0[j + 1] = row0[j] + job.m;
+        max_m = std::max(max_m, job.m);
+    }
+    auto a256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t o_jobs = 0, o_row0 = o_jobs + a256(jobs.size() * sizeof(lcsgpu::GroupPrimJob)), o_ids = o_row0 + a256(row0.size() * 8),
+                 o_edges = o_ids + a256((size_t)n_total * 4), o_sq = o_edges + a256((size_t)n_edges * sizeof(lcsgpu_mst_edge)),
+                 total = o_sq + (use_square ? a256((size_t)sq_elems * 2) : 0);
+    rc = reserve_big(ctx, L.d_work, total, "the batched MST's tables");
+    if (rc) return rc;
+    char* base = (char*)L.d_work.p;
+    HIP_TRY(hipMemcpyAsync(base + o_jobs, jobs.data(), jobs.size() * sizeof(lcsgpu::GroupPrimJob), hipMemcpyHostToDevice, L.stream));
+    HIP_TRY(hipMemcpyAsync(base + o_row0, row0.data(), row0.size() * 8, hipMemcpyHostToDevice, L.stream));
+    HIP_TRY(hipMemcpyAsync(base + o_ids, ids, (size_t)n_total * 4, hipMemcpyHostToDevice, L.stream));
+    lcsgpu::GroupPrimArgs a{};
+    a.tri = (const uint16_t*)L.d_out.p;
+    a.sq = use_square ? (uint16_t*)(base + o_sq) : nullptr;
+    a.jobs = (const lcsgpu::GroupPrimJob*)(base + o_jobs);
+    a.row0 = (const int64_t*)(base + o_row0);
+    a.ids = (const int32_t*)(base + o_ids);
+    a.lens = (const uint32_t*)ctx->d_lens.p;
+    a.pow_table = (const double*)ctx->d_pow.p;
+    a.edges = (lcsgpu::MstEdge*)(base + o_edges);
+    a.total_rows = row0.back();
+    a.pow_n = (int32_t)(2 * (size_t)ctx->max_len + 1);
+    a.n_jobs = (int32_t)jobs.size();
+    a.kind = distance_kind;
+    a.max_m = max_m;
+    if (const hipError_t e = lcsgpu::launch_group_prim(a, L.stream))
+        return fail(LCSGPU_E_HIP, "the batched MST's launch failed: %s", hipGetErrorString(e));
+    if (!had_long) { // the call's kernel time: the triangles' launches and this one
+        HIP_TRY(hipEventRecord(L.ev_stop, L.stream));
+        L.last_launches += use_square ? 2 : 1;
+    }
+    HIP_TRY(hipEventRecord(L.ev_done, L.stream));
+    HIP_TRY(hipEventSynchronize(L.ev_done));
+    if (hold.held) {
+        hold.g.unlock_shared();
+        hold.held = false;
+    }
+    static_assert(sizeof(lcsgpu_mst_edge) == sizeof(lcsgpu::MstEdge), "edge records");
+    HIP_TRY(hipMemcpy(out_edges, base + o_edges, (size_t)n_edges * sizeof(lcsgpu_mst_edge), hipMemcpyDeviceToHost));
+    if (!had_long) finish_host_call(ctx, L);
+    else L.plan_in_flight = false;
+    return LCSGPU_OK;
+}
+
+int lcsgpu_mst_prim_batch(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* group_offsets, int32_t n_groups, int distance_kind,
+                          lcsgpu_mst_edge* out_edges)
+{
+    try {
+        return mst_prim_batch_impl(ctx, ids, group_offsets, n_groups, distance_kind, out_edges);
+    } catch (const std::exception& e) { // no exception leaves the C-ABI
+        return fail(LCSGPU_E_NOMEM, "batched MST: %s", e.what());
+    }
+}
+
 int lcsgpu_assign_seeds(lcsgpu_ctx* ctx, const int32_t* seed_ids, int32_t n_seeds, const int32_t* col_ids,
                         int32_t n_cols, int distance_kind, int32_t first_k, float* dist, int32_t* assign)
 {

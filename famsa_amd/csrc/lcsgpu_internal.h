@@ -33,7 +33,8 @@ int fail(int code, const char* fmt, ...);
 // search chains ends after that long and the chains continue in the next: 0 = none, a test aid), clarans_large_slice_us (the same
 // for the chains of clarans_large_chain_kernel, where it is on by default: 250000), clarans_draws (step positions
 // drawn for a sample shape before its first launch, 65536), assign_batch_kb (LCS rectangles of one launch of the batched seed
-// assignment, 2 GB), upgma_spare (spare slots of the UPGMA matrix, n / 10)
+// assignment, 2 GB), upgma_spare (spare slots of the UPGMA matrix, n / 10), mst_batch_square (1, the default: lcsgpu_mst_prim_batch
+// expands every group's triangle to a square first; 0: it reads the packed triangles -- measurements)
 int tune_int(const char* key, int dflt);
 
 #define HIP_TRY(expr)                                                                           \

@@ -34,6 +34,7 @@
 #include <type_traits>
 
 #include "lcs_kernels.h"
+#include "fasttree_kernels.h"
 
 namespace lcsgpu {
 
@@ -712,6 +713,183 @@ hipError_t launch_boruvka_fuse_reset(const BoruvkaArgs& a, bool keep, hipStream_
 hipError_t launch_boruvka_fuse_fold(const BoruvkaArgs& a, hipStream_t stream)
 {
     hipLaunchKernelGGL(boruvka_fuse_fold_kernel, dim3((a.n + 255) / 256), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
+// ---- Prim's MST of many small groups in one launch (lcsgpu_mst_prim_batch) ------------------------------------------
+// ONE WORKGROUP PER GROUP runs MSTPrim's recurrence (reference tree/MSTPrim.cpp:356-533) from member 0 to its end: m - 1
+// steps of (1) every thread relaxes the alive vertices it owns (v = thread, thread + THREADS, ...) against the vertex
+// just added, (2) the workgroup's smallest alive key, (3) the winner's record.  A group of a few hundred members is all
+// latency to the Boruvka rounds of lcsgpu_mst_prim (about eight rounds of five or more launches, one busy CU); here the
+// whole tree costs one launch, and the groups of a batch fill the chip side by side.
+// Per-vertex state in LDS: key distance bits (DEAD = no longer alive), key partner, length -- 14 B per vertex, what caps a
+// group at MST_GROUP_MAX_MEMBERS.  A vertex's state is only ever touched by its owner; what crosses threads are the
+// lengths (read-only after the first barrier) and the per-wave minima, which alternate between two sets of slots by step
+// parity: a wave writes set p again only two barriers after anybody read it, so ONE barrier per step is enough.
+// No workgroup waits for another one, and every loop's bound is known at launch.
+// SQUARE: the LCS values of (cur, v) come from row cur of the group's m x m square (contiguous) instead of the packed
+// triangle, where those of v > cur are a strided 2-byte gather at v (v - 1) / 2 + cur.
+constexpr unsigned long long DEAD = ~0ull;
+
+template <int THREADS>
+constexpr size_t group_prim_lds_bytes(int cap, int pow_n)
+{
+    // the waves' two sets of (d, id, vertex), the pow table when it is staged, then the vertices
+    return (size_t)2 * (THREADS / 64) * 20 + (size_t)pow_n * 8 + (size_t)cap * 14;
+}
+constexpr size_t GROUP_PRIM_LDS_MAX = 64 * 1024;
+
+__global__ __launch_bounds__(256) void mst_group_square_kernel(GroupPrimArgs a)
+{
+    // which job this row belongs to: the last one whose first row is <= the block's
+    const int64_t row = blockIdx.x;
+    int lo = 0, hi = a.n_jobs - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (a.row0[mid] <= row) lo = mid; else hi = mid - 1;
+    }
+    const GroupPrimJob job = a.jobs[lo];
+    const int m = job.m, i = (int)(row - a.row0[lo]);
+    if (i >= m) return;
+    const uint16_t* tri = a.tri + job.tri0;
+    uint16_t* out = a.sq + job.sq0 + (int64_t)i * m;
+    for (int j = threadIdx.x; j < m; j += 256) {
+        const int64_t h = i > j ? i : j, l = i > j ? j : i;
+        out[j] = i == j ? (uint16_t)0 : tri[h * (h - 1) / 2 + l];
+    }
+}
+
+// POW_LDS: the pow table staged in LDS (it fits beside the vertices of every launch the host layer routes here: 6.4 KB for
+// sequences up to 400 residues) -- else the exact key costs a second, dependent global load per candidate.
+template <int KIND, bool SQUARE, int THREADS, bool POW_LDS>
+__global__ __launch_bounds__(THREADS) void mst_group_prim_kernel(GroupPrimArgs a)
+{
+    constexpr int WAVES = THREADS / 64;
+    constexpr int UNR = 4; // vertices of a thread whose LCS loads are in flight together: a step is their latency
+    extern __shared__ unsigned long long s_group[];
+    unsigned long long* s_wd = s_group;              // [2][WAVES] the waves' smallest keys: distance bits,
+    unsigned long long* s_wid = s_wd + 2 * WAVES;    //            id,
+    int* s_wv = (int*)(s_wid + 2 * WAVES);           //            vertex (2 x WAVES ints = WAVES x 8 B)
+    double* s_pow = (double*)(s_wid + 2 * WAVES + WAVES); // [pow_n] when POW_LDS
+    unsigned long long* s_kd = (unsigned long long*)(s_pow + (POW_LDS ? a.pow_n : 0)); // [max_m]
+    uint32_t* s_partner = (uint32_t*)(s_kd + a.max_m);
+    uint16_t* s_len = (uint16_t*)(s_partner + a.max_m);
+
+    const GroupPrimJob job = a.jobs[blockIdx.x];
+    const int m = job.m;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint16_t* lcs = SQUARE ? a.sq + job.sq0 : a.tri + job.tri0;
+    if (POW_LDS)
+        for (int i = tid; i < a.pow_n; i += THREADS) s_pow[i] = a.pow_table[i];
+    const PowTable<POW_LDS> pw{POW_LDS ? s_pow : a.pow_table};
+    for (int v = tid; v < m; v += THREADS) {
+        s_len[v] = (uint16_t)a.lens[a.ids[job.id0 + v]];
+        s_kd[v] = v == 0 ? DEAD : NO_D; // (MSTPrim's initial key: DBL_MAX, beaten by every distance)
+        s_partner[v] = 0;
+    }
+    __syncthreads();
+    int cur = 0;
+    for (int step = 0; step + 1 < m; ++step) {
+        const uint32_t len_c = s_len[cur];
+        const int64_t row_c = SQUARE ? (int64_t)cur * m : (int64_t)cur * (cur - 1) / 2;
+        unsigned long long bd = DEAD, bi = NO_ID;
+        int bv = -1;
+        for (int v0 = tid; v0 < m; v0 += THREADS * UNR) {
+            unsigned long long kds[UNR];
+            uint32_t ls[UNR];
+#pragma unroll
+            for (int k = 0; k < UNR; ++k) { // the loads first (a vertex that is gone or past the end reads element 0: m >= 2 has one)
+                const int v = v0 + k * THREADS;
+                kds[k] = v < m ? s_kd[v] : DEAD;
+                const int64_t at = kds[k] == DEAD ? 0 : SQUARE || v < cur ? row_c + v : (int64_t)v * (v - 1) / 2 + cur;
+                ls[k] = lcs[at];
+            }
+#pragma unroll
+            for (int k = 0; k < UNR; ++k) {
+                const int v = v0 + k * THREADS;
+                unsigned long long kd = kds[k];
+                if (kd == DEAD) continue;
+                uint32_t partner = s_partner[v];
+                const uint32_t l = ls[k];
+                const uint32_t indel = min(len_c + s_len[v] - 2u * l, (uint32_t)a.pow_n - 1u);
+                // the candidate (cur, v): exact_update's arithmetic -- Transform<double, KIND> (hpp:28-82), and before the
+                // division the multiplication that proves most candidates strictly worse than the key v already has
+                const double p = KIND == 1 ? pw(indel) : (double)indel;
+                unsigned long long db;
+                if (l == 0) db = (unsigned long long)__double_as_longlong(1.7976931348623155e308); // nextafter(DBL_MAX, 0), hpp:61,73
+                else if (p > (__longlong_as_double((long long)kd) * (double)l) * (1.0 + 0x1p-50)) db = DEAD;
+                else db = (unsigned long long)__double_as_longlong(p / (double)l);
+                if (db != DEAD && (db < kd || (db == kd && pack_ids((uint32_t)cur, (uint32_t)v) > pack_ids(partner, (uint32_t)v)))) {
+                    kd = db;
+                    partner = (uint32_t)cur;
+                    s_kd[v] = kd;
+                    s_partner[v] = partner;
+                }
+                const unsigned long long kid = ~pack_ids(partner, (uint32_t)v);
+                if (key_less(kd, kid, bd, bi)) { bd = kd; bi = kid; bv = v; }
+            }
+        }
+        // the wave's smallest key into this step's set of slots: the ids of alive vertices differ (a pair has one alive
+        // end), so one lane holds it -- or none does (no alive vertex among the wave's) and lane 0 says so
+        unsigned long long wd = bd, wid = bi;
+        wave_min_key(wd, wid);
+        const int set = (step & 1) * WAVES;
+        if (wd == DEAD) {
+            if (lane == 0) { s_wd[set + wave] = DEAD; s_wid[set + wave] = NO_ID; s_wv[set + wave] = -1; }
+        } else if (bd == wd && bi == wid) {
+            s_wd[set + wave] = wd;
+            s_wid[set + wave] = wid;
+            s_wv[set + wave] = bv;
+        }
+        __syncthreads();
+        unsigned long long gd = s_wd[set], gi = s_wid[set];
+        int gv = s_wv[set];
+#pragma unroll
+        for (int w = 1; w < WAVES; ++w) {
+            const unsigned long long d2 = s_wd[set + w], i2 = s_wid[set + w];
+            if (key_less(d2, i2, gd, gi)) { gd = d2; gi = i2; gv = s_wv[set + w]; }
+        }
+        if (gv < 0 || gv >= m) return; // (cannot happen while a vertex is alive; uniform across the workgroup)
+        if (tid == 0) {
+            const unsigned long long packed = ~gi;
+            MstEdge e;
+            e.from = (int32_t)(packed >> 32);
+            e.to = (int32_t)(packed & 0xffffffffull);
+            e.dist = __longlong_as_double((long long)gd);
+            a.edges[job.edge0 + step] = e;
+        }
+        if ((gv & (THREADS - 1)) == tid) s_kd[gv] = DEAD; // by its owner
+        cur = gv;
+    }
+}
+
+hipError_t launch_group_prim(const GroupPrimArgs& a, hipStream_t stream)
+{
+    if (a.n_jobs <= 0) return hipSuccess;
+    if (a.max_m < 2 || a.max_m > MST_GROUP_MAX_MEMBERS) return hipErrorInvalidValue;
+    const bool square = a.sq != nullptr;
+    if (square) {
+        if (a.total_rows <= 0 || a.total_rows > 0x7fffffff) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(mst_group_square_kernel, dim3((unsigned)a.total_rows), dim3(256), 0, stream, a);
+    }
+    // four waves up to 1024 members (a step is latency, and a barrier over four waves is the shortest), sixteen beyond:
+    // the gathers of a step in flight at once
+    const dim3 grid((unsigned)a.n_jobs);
+    const bool wide = a.max_m > 1024;
+    const bool pow_lds = a.kind == 1 && (wide ? group_prim_lds_bytes<1024>(a.max_m, a.pow_n) : group_prim_lds_bytes<256>(a.max_m, a.pow_n)) <= GROUP_PRIM_LDS_MAX;
+#define GROUP_PRIM(K, S, T, P)                                                                                       \
+    hipLaunchKernelGGL((mst_group_prim_kernel<K, S, T, P>), grid, dim3(T), group_prim_lds_bytes<T>(a.max_m, P ? a.pow_n : 0), stream, a)
+#define GROUP_PRIM_T(K, S, P)                                                                                        \
+    if (!wide) GROUP_PRIM(K, S, 256, P); else GROUP_PRIM(K, S, 1024, P)
+    if (a.kind != 1) { // (no table: the numerator is the integer)
+        if (square) { GROUP_PRIM_T(0, true, false); } else { GROUP_PRIM_T(0, false, false); }
+    } else if (pow_lds) {
+        if (square) { GROUP_PRIM_T(1, true, true); } else { GROUP_PRIM_T(1, false, true); }
+    } else {
+        if (square) { GROUP_PRIM_T(1, true, false); } else { GROUP_PRIM_T(1, false, false); }
+    }
+#undef GROUP_PRIM_T
+#undef GROUP_PRIM
     return hipGetLastError();
 }
 

@@ -1,0 +1,451 @@
+#include "batch.h"
+
+#include <algorithm>
+#include <chrono>
+#include <condition_variable>
+#include <deque>
+#include <future>
+#include <memory>
+#include <mutex>
+#include <stdexcept>
+#include <thread>
+
+namespace famsa_host {
+
+namespace {
+
+double now_s()
+{
+    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+// The planner's step, shared by batch_plan and the driver (which learns the unique counts file by file, in order).
+struct ChunkPacker {
+    int64_t budget;
+    int group_max;
+    int chunk = -1;
+    int64_t used = 0;
+    int place(int64_t m, bool eligible)
+    {
+        if (!eligible || m > group_max) return -1;
+        const int64_t pairs = m > 1 ? m * (m - 1) / 2 : 0;
+        if (chunk < 0 || used + pairs > budget) {
+            ++chunk;
+            used = 0;
+        }
+        used += pairs;
+        return chunk;
+    }
+};
+
+// worker threads of the batch: loading + sorting files, and turning a chunk's device results into Newick texts
+class Pool {
+public:
+    explicit Pool(int n_threads)
+    {
+        for (int t = 0; t < std::max(1, n_threads); ++t) threads_.emplace_back([this] { work(); });
+    }
+    ~Pool()
+    {
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            stop_ = true;
+        }
+        cv_.notify_all();
+        for (auto& t : threads_) t.join();
+    }
+    void submit(std::function<void()> task)
+    {
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            tasks_.push_back(std::move(task));
+            ++pending_;
+        }
+        cv_.notify_one();
+    }
+    void wait_idle()
+    {
+        std::unique_lock<std::mutex> lk(mu_);
+        idle_.wait(lk, [this] { return pending_ == 0; });
+    }
+
+private:
+    void work()
+    {
+        for (;;) {
+            std::function<void()> task;
+            {
+                std::unique_lock<std::mutex> lk(mu_);
+                cv_.wait(lk, [this] { return stop_ || !tasks_.empty(); });
+                if (tasks_.empty()) return;
+                task = std::move(tasks_.front());
+                tasks_.pop_front();
+            }
+            task(); // (tasks catch what they throw)
+            {
+                std::lock_guard<std::mutex> lk(mu_);
+                --pending_;
+            }
+            idle_.notify_all();
+        }
+    }
+    std::vector<std::thread> threads_;
+    std::deque<std::function<void()>> tasks_;
+    std::mutex mu_;
+    std::condition_variable cv_, idle_;
+    int pending_ = 0;
+    bool stop_ = false;
+};
+
+// A file's slice of a chunk as the tree builders see it: ids 0 .. m - 1 = the file's sorted unique working order.  Prim's
+// edges come from the chunk's lcsgpu_mst_prim_batch, the triangle from its lcsgpu_lcs_triangles_batch; nothing is computed here.
+class SliceLcsSource : public LcsSource {
+public:
+    SliceLcsSource(const SeqSet& s, const std::vector<int>& in_of, bool sensitive) : s_(s), in_of_(in_of), sensitive_(sensitive) {}
+    const uint16_t* tri = nullptr;   // the slice's packed triangle, or NULL
+    const MstEdge* edges = nullptr;  // its m - 1 MST records, or NULL
+    int edges_kind = -1;
+    bool edges_triangle_orientation = false;
+
+    int n() const override { return (int)in_of_.size(); }
+    uint32_t length(int i) const override { return s_.length((size_t)in_of_[(size_t)i]); }
+    bool orientation_sensitive() const override { return sensitive_; }
+    bool wide() const override { return false; } // (a chunk takes no file with a sequence beyond 65535 residues)
+    bool whole_input() const override { return true; }
+    const void* triangle_view() const override { return tri; }
+    void triangle(int r0, int r1, LcsBuf& out) override
+    {
+        if (!tri) throw std::runtime_error("batch: the chunk holds no LCS triangle for this file");
+        const size_t a = (size_t)r0 * (r0 > 0 ? r0 - 1 : 0) / 2, b = (size_t)r1 * (r1 > 0 ? r1 - 1 : 0) / 2;
+        out.resize(b - a, false);
+        std::copy(tri + a, tri + b, out.v16.begin());
+    }
+    void rect(const int*, int, const int*, int, LcsBuf&) override
+    {
+        throw std::runtime_error("batch: a chunk serves triangles and MST records only");
+    }
+    bool prim_edges(int distance_kind, std::vector<MstEdge>& out, bool triangle_orientation) override
+    {
+        if (!edges || distance_kind != edges_kind || triangle_orientation != edges_triangle_orientation) return false;
+        out.assign(edges, edges + (n() > 0 ? n() - 1 : 0));
+        return true;
+    }
+
+private:
+    const SeqSet& s_;
+    const std::vector<int>& in_of_;
+    bool sensitive_;
+};
+
+struct Loaded {
+    SeqSet s;
+    WorkSet w;
+    std::vector<int> in_of; // unique index -> record of the file
+    bool ok = false, eligible = false;
+    std::string message;
+};
+
+bool is_mst(GT m) { return m == GT::MST_Prim || m == GT::SLINK; }
+
+} // namespace
+
+int64_t batch_pair_budget()
+{
+    // 2 GiB of uint16 values: what the batched rectangles of the seed assignment take per launch (assign_batch_kb)
+    return (int64_t)std::max(1, host_test_int("batch_pairs", 1 << 30));
+}
+
+int batch_group_max()
+{
+    // The largest measured family size at which the chunks are ahead of both the one-file route on the same context and a
+    // guide_tree loop, for -gt sl and for -gt upgma (profiles/batch_trees.txt: 849 / 316 files/s against 322 / 169 and 51 / 51
+    // at 1000 members; at 4000 -gt upgma gains nothing); never above LCSGPU_MST_BATCH_MAX_MEMBERS.
+    return std::max(0, std::min(4096, host_test_int("batch_group_max", 1000)));
+}
+
+int batch_plan(const std::vector<int64_t>& unique_counts, const std::vector<uint8_t>& eligible, int64_t pair_budget, int group_max,
+               std::vector<int>& chunk_of)
+{
+    ChunkPacker packer{pair_budget, std::min(group_max, 4096)};
+    chunk_of.assign(unique_counts.size(), -1);
+    for (size_t i = 0; i < unique_counts.size(); ++i) chunk_of[i] = packer.place(unique_counts[i], i < eligible.size() && eligible[i] != 0);
+    return packer.chunk + 1;
+}
+
+std::vector<BatchResult> guide_trees_newick_gpu(const std::vector<BatchJob>& jobs, int device, BatchTotals* totals, EngineFuture* engine,
+                                                const std::function<void(size_t, const BatchResult&)>& done)
+{
+    const size_t n = jobs.size();
+    std::vector<BatchResult> results(n);
+    BatchTotals tot;
+    tot.files = (int)n;
+    if (n == 0) {
+        if (totals) *totals = tot;
+        return results;
+    }
+    EngineFuture own;
+    if (!engine) {
+        own = start_engine(device); // HIP initialisation runs beside the first loads
+        engine = &own;
+    }
+    int n_threads = jobs[0].opt.fast.n_threads;
+    for (const auto& j : jobs) n_threads = std::min(n_threads, j.opt.fast.n_threads);
+    n_threads = std::max(1, n_threads);
+
+    std::mutex tot_mu; // the totals the workers add to
+    std::vector<std::shared_ptr<Loaded>> loaded(n);
+    std::vector<std::future<void>> load_done(n);
+    auto finish = [&](size_t i, BatchResult&& r) {
+        results[i] = std::move(r);
+        if (done) done(i, results[i]);
+    };
+    auto fail_file = [&](size_t i, const std::string& why, int route) {
+        BatchResult r;
+        r.message = why;
+        r.route = route;
+        {
+            std::lock_guard<std::mutex> lk(tot_mu);
+            ++tot.failed;
+        }
+        finish(i, std::move(r));
+    };
+
+    auto load_one = [&](size_t i) {
+        auto f = std::make_shared<Loaded>();
+        const TreeOptions& opt = jobs[i].opt;
+        try {
+            const double t0 = now_s();
+            f->s = load_fasta(jobs[i].input, 1);
+            if (f->s.size() == 0) throw std::runtime_error("no sequences in " + jobs[i].input);
+            const double t1 = now_s();
+            f->w = make_workset(f->s, opt.keep_duplicates, 1);
+            f->in_of.resize((size_t)f->w.n_unique());
+            for (int a = 0; a < f->w.n_unique(); ++a) f->in_of[(size_t)a] = f->w.sorted2input[(size_t)f->w.unique2sorted[(size_t)a]];
+            uint32_t longest = 0;
+            for (size_t r = 0; r < f->s.size(); ++r) longest = std::max(longest, f->s.length(r));
+            // what guide_tree_newick decides for the file alone: a heuristic applies from the threshold on (all records count)
+            const bool heuristic = opt.heuristic != 0 && (int)f->s.size() >= opt.fast.threshold;
+            f->eligible = longest <= 65535 && !heuristic && opt.method != GT::chained &&
+                          (opt.dist == Distance::indel_div_lcs || opt.dist == Distance::indel075_div_lcs);
+            f->ok = true;
+            const double t2 = now_s();
+            std::lock_guard<std::mutex> lk(tot_mu);
+            tot.load_s += t1 - t0;
+            tot.sort_s += t2 - t1;
+        } catch (const std::exception& e) {
+            f->message = e.what();
+        }
+        loaded[i] = f;
+    };
+
+    Pool pool(n_threads);
+    size_t submitted = 0;
+    const size_t lookahead = 256; // files loaded ahead of the chunk the device works on
+    auto submit_loads = [&](size_t upto) {
+        for (; submitted < std::min(n, upto); ++submitted) {
+            const size_t i = submitted;
+            auto pr = std::make_shared<std::promise<void>>();
+            load_done[i] = pr->get_future();
+            pool.submit([&load_one, i, pr] {
+                load_one(i);
+                pr->set_value();
+            });
+        }
+    };
+
+    std::unique_ptr<GpuLcsSource> held;
+    std::string engine_error;
+    auto the_engine = [&]() -> GpuLcsSource* {
+        if (!held && engine_error.empty()) {
+            try {
+                held = engine->get();
+            } catch (const std::exception& e) {
+                engine_error = e.what();
+            }
+        }
+        return held.get();
+    };
+
+    std::vector<size_t> one_file; // in list order; the chunks add the -gt sl files they find an orientation-sensitive member in
+
+    // what a chunk's device calls leave behind for the workers
+    struct ChunkData {
+        std::vector<LcsSource::MstEdge> edges[4]; // by (triangle orientation, distance kind)
+        LcsBuf tri;
+    };
+    auto run_chunk = [&](const std::vector<size_t>& files) {
+        GpuLcsSource* src = the_engine();
+        if (!src) {
+            for (size_t i : files) fail_file(i, engine_error, 0);
+            return;
+        }
+        std::vector<size_t> pending = files; // not finished yet: what an error of the chunk's calls fails
+        try {
+            const double t0 = now_s();
+            // the chunk's records, file after file as they were read; ids = every file's sorted unique order, one after the other
+            size_t n_records = 0, n_codes = 0, n_ids = 0;
+            for (size_t i : files) {
+                n_records += loaded[i]->s.size();
+                n_codes += loaded[i]->s.codes.size();
+                n_ids += loaded[i]->in_of.size();
+            }
+            if (n_records > 0x7fffffffu || n_ids > 0x7fffffffu) throw std::runtime_error("batch: a chunk of more than 2^31 records");
+            Bytes codes(n_codes);
+            std::vector<uint64_t> offsets;
+            offsets.reserve(n_records + 1);
+            std::vector<int> order;
+            order.reserve(n_ids);
+            std::vector<int> id0(files.size());
+            size_t code_at = 0, rec_at = 0;
+            for (size_t k = 0; k < files.size(); ++k) {
+                const Loaded& f = *loaded[files[k]];
+                std::copy(f.s.codes.begin(), f.s.codes.end(), codes.begin() + (ptrdiff_t)code_at);
+                for (size_t r = 0; r < f.s.size(); ++r) offsets.push_back(f.s.offsets[r] + code_at);
+                id0[k] = (int)order.size();
+                for (int rec : f.in_of) order.push_back((int)rec_at + rec);
+                code_at += f.s.codes.size();
+                rec_at += f.s.size();
+            }
+            offsets.push_back(code_at);
+            src->upload_ordered(codes.data(), offsets, order);
+            const std::vector<uint8_t>& flags = src->orientation_flags();
+            const double t1 = now_s();
+
+            auto data = std::make_shared<ChunkData>();
+            std::vector<char> sensitive(files.size(), 0);
+            std::vector<int> list_of(files.size(), -1);     // which of the five requests serves the file (4 = the triangles)
+            std::vector<size_t> at(files.size(), 0);        // where its records / its triangle start in that request's result
+            std::vector<std::vector<int>> ids(5);
+            std::vector<std::vector<int64_t>> offs(5, std::vector<int64_t>{0});
+            std::vector<size_t> filled(5, 0);
+            for (size_t k = 0; k < files.size(); ++k) {
+                const size_t i = files[k];
+                const Loaded& f = *loaded[i];
+                const TreeOptions& opt = jobs[i].opt;
+                const int m = (int)f.in_of.size();
+                for (int a = 0; a < m; ++a) sensitive[k] |= flags[(size_t)(id0[k] + a)] != 0;
+                if (m < 2) continue; // one unique sequence: no tree stage (guide_tree_newick)
+                int list;
+                if (opt.method == GT::MST_Prim && sensitive[k]) { // MSTPrim wants LCS(ref = the node just added): not in a triangle
+                    one_file.push_back(i);
+                    pending.erase(std::find(pending.begin(), pending.end(), i));
+                    list_of[k] = -2;
+                    continue;
+                }
+                if (is_mst(opt.method)) list = (opt.method == GT::SLINK ? 2 : 0) + (opt.dist == Distance::indel075_div_lcs ? 1 : 0);
+                else list = 4;
+                list_of[k] = list;
+                at[k] = filled[(size_t)list];
+                filled[(size_t)list] += list == 4 ? (size_t)m * (m - 1) / 2 : (size_t)(m - 1);
+                for (int a = 0; a < m; ++a) ids[(size_t)list].push_back(id0[k] + a);
+                offs[(size_t)list].push_back((int64_t)ids[(size_t)list].size());
+            }
+            for (int list = 0; list < 4; ++list)
+                if (offs[(size_t)list].size() > 1)
+                    src->prim_edges_batch(ids[(size_t)list].data(), offs[(size_t)list].data(), (int)offs[(size_t)list].size() - 1, list & 1,
+                                          list >= 2, data->edges[list]);
+            if (offs[4].size() > 1) src->triangles_batch(ids[4].data(), offs[4].data(), (int)offs[4].size() - 1, data->tri);
+            const double t2 = now_s();
+            {
+                std::lock_guard<std::mutex> lk(tot_mu);
+                tot.upload_s += t1 - t0;
+                tot.device_s += t2 - t1;
+                ++tot.chunks;
+            }
+            // the conversions of the chunk's files, on the workers; the next chunk's upload does not touch what they read
+            for (size_t k = 0; k < files.size(); ++k) {
+                if (list_of[k] == -2) continue;
+                const size_t i = files[k];
+                const int list = list_of[k];
+                const size_t where = at[k];
+                const bool sens = sensitive[k] != 0;
+                pool.submit([&, i, list, where, sens, data] {
+                    std::shared_ptr<Loaded> f = loaded[i];
+                    try {
+                        const double c0 = now_s();
+                        SliceLcsSource view(f->s, f->in_of, sens);
+                        if (list == 4) view.tri = data->tri.v16.data() + where;
+                        else if (list >= 0) {
+                            view.edges = data->edges[list].data() + where;
+                            view.edges_kind = list & 1;
+                            view.edges_triangle_orientation = list >= 2;
+                        }
+                        BatchResult r;
+                        r.newick = guide_tree_newick(f->s, f->w, view, jobs[i].opt);
+                        r.ok = true;
+                        r.route = 0;
+                        {
+                            std::lock_guard<std::mutex> lk(tot_mu);
+                            tot.newick_s += now_s() - c0;
+                            ++tot.in_chunks;
+                        }
+                        finish(i, std::move(r));
+                    } catch (const std::exception& e) {
+                        fail_file(i, e.what(), 0);
+                    }
+                    loaded[i].reset();
+                });
+            }
+        } catch (const std::exception& e) {
+            for (size_t i : pending) fail_file(i, e.what(), 0);
+        }
+    };
+
+    ChunkPacker packer{batch_pair_budget(), batch_group_max()};
+    std::vector<size_t> current;
+    int current_chunk = -1;
+    for (size_t i = 0; i < n; ++i) {
+        submit_loads(i + lookahead);
+        load_done[i].get();
+        const Loaded& f = *loaded[i];
+        if (!f.ok) {
+            fail_file(i, f.message, -1);
+            loaded[i].reset();
+            continue;
+        }
+        const int c = packer.place(f.w.n_unique(), f.eligible);
+        if (c < 0) {
+            one_file.push_back(i);
+            continue;
+        }
+        if (c != current_chunk && !current.empty()) { // the chunk is full: the device takes it while the workers load on
+            run_chunk(current);
+            current.clear();
+        }
+        current_chunk = c;
+        current.push_back(i);
+    }
+    if (!current.empty()) run_chunk(current);
+
+    // everything else: today's one-file path, one after the other, on the same engine
+    std::sort(one_file.begin(), one_file.end());
+    for (size_t i : one_file) {
+        GpuLcsSource* src = the_engine();
+        if (!src) {
+            fail_file(i, engine_error, 1);
+            continue;
+        }
+        try {
+            const double t0 = now_s();
+            BatchResult r;
+            r.newick = guide_tree_newick_gpu(loaded[i]->s, *src, jobs[i].opt, nullptr);
+            r.ok = true;
+            r.route = 1;
+            {
+                std::lock_guard<std::mutex> lk(tot_mu);
+                tot.one_file_s += now_s() - t0;
+                ++tot.one_file;
+            }
+            finish(i, std::move(r));
+        } catch (const std::exception& e) {
+            fail_file(i, e.what(), 1);
+        }
+        loaded[i].reset();
+    }
+    pool.wait_idle();
+    if (g_abandon_engine_at_return && !profile_on()) (void)held.release();
+    if (totals) *totals = tot;
+    return results;
+}
+
+} // namespace famsa_host

@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "batch.h"
 #include "lcs_source.h"
 #include "pipeline.h"
 #include "seqset.h"
@@ -20,6 +21,7 @@ using namespace famsa_host;
 
 namespace {
 thread_local std::string g_error;
+thread_local std::vector<std::string> g_batch_messages; // per file, of this thread's last famsa_host_trees_gpu
 
 // heuristic: 0 none, 1 parttree, 2 medoidtree; the int/float params override CParams::medoid when > 0
 TreeOptions make_options(const char* method, int distance, int keep_duplicates, int heuristic, int subtree_size,
@@ -142,6 +144,62 @@ long famsa_host_tree_gpu(const char* fasta, int device, const char* method, int 
                                                         sample_size, threshold, cluster_fraction, cluster_iters),
                                            nullptr),
                     out, cap);
+    } catch (const std::exception& e) {
+        return fail(e);
+    }
+}
+
+// Guide trees of many FASTA files on ONE engine context (batch.h): the same options for every file.  out receives the
+// Newick texts one after the other (no separators, NUL after the last), offsets[n + 1] where file i's text starts and
+// ends, status[i] = 0 (made) or -1 (failed: famsa_host_trees_message(i) says why; the others are still made).
+// Returns the bytes of all texts; -1 on an error of the call itself; too small a buffer: -(bytes needed) - 1.
+long famsa_host_trees_gpu(const char* const* fastas, int n_files, int device, const char* method, int distance, int keep_duplicates,
+                          int heuristic, int subtree_size, int sample_size, int threshold, float cluster_fraction,
+                          int cluster_iters, char* out, long cap, int64_t* offsets, int* status)
+{
+    try {
+        if (n_files < 0 || (n_files > 0 && (!fastas || !offsets || !status))) throw std::runtime_error("famsa_host_trees_gpu: bad argument");
+        const TreeOptions o = make_options(method, distance, keep_duplicates, heuristic, subtree_size, sample_size, threshold,
+                                           cluster_fraction, cluster_iters);
+        std::vector<BatchJob> jobs((size_t)n_files);
+        for (int i = 0; i < n_files; ++i) {
+            if (!fastas[i]) throw std::runtime_error("famsa_host_trees_gpu: NULL path");
+            jobs[(size_t)i].input = fastas[i];
+            jobs[(size_t)i].opt = o;
+        }
+        const std::vector<BatchResult> res = guide_trees_newick_gpu(jobs, device);
+        g_batch_messages.assign((size_t)n_files, std::string());
+        std::string all;
+        for (int i = 0; i < n_files; ++i) {
+            offsets[i] = (int64_t)all.size();
+            status[i] = res[(size_t)i].ok ? 0 : -1;
+            if (res[(size_t)i].ok) all += res[(size_t)i].newick;
+            else g_batch_messages[(size_t)i] = res[(size_t)i].message;
+        }
+        if (n_files >= 0 && offsets) offsets[n_files] = (int64_t)all.size();
+        return give(all, out, cap);
+    } catch (const std::exception& e) {
+        return fail(e);
+    }
+}
+
+const char* famsa_host_trees_message(int i)
+{
+    return i >= 0 && (size_t)i < g_batch_messages.size() ? g_batch_messages[(size_t)i].c_str() : "";
+}
+
+// The chunk planner of the batch on its own (no GPU): chunk_of[i] = the chunk file i goes into, -1 = the one-file route.
+// pair_budget / group_max <= 0: the defaults.  Returns the number of chunks, -1 on error.
+int famsa_host_batch_plan(const int64_t* unique_counts, const uint8_t* eligible, int n_files, int64_t pair_budget, int group_max,
+                          int* chunk_of)
+{
+    try {
+        if (n_files < 0 || (n_files > 0 && (!unique_counts || !eligible || !chunk_of))) throw std::runtime_error("famsa_host_batch_plan: bad argument");
+        std::vector<int> plan;
+        const int chunks = batch_plan(std::vector<int64_t>(unique_counts, unique_counts + n_files), std::vector<uint8_t>(eligible, eligible + n_files),
+                                      pair_budget > 0 ? pair_budget : batch_pair_budget(), group_max > 0 ? group_max : batch_group_max(), plan);
+        for (int i = 0; i < n_files; ++i) chunk_of[i] = plan[(size_t)i];
+        return chunks;
     } catch (const std::exception& e) {
         return fail(e);
     }

@@ -1,6 +1,11 @@
 // famsa-gpu -- the guide-tree / distance-export front end of FAMSA on the MI355X LCS engine.
 // Accepts the reference CLI's flags for this path (reference core/params.cpp:136-294, help text
 // :60-134):   famsa-gpu [options] <input.fasta> <output>
+//              famsa-gpu [tree options] -gt_export -batch <list>
+//   -batch <list>                            guide trees for many files in ONE process on one engine context: <list> is a
+//                                            text file of "input<TAB>output" lines (blank lines and lines starting with '#'
+//                                            are skipped); every output is what the one-file command writes for that input.
+//                                            Not with -dist_export, -stats, -dump_seeds, several GPUs or positional arguments
 //   -gt <sl|slink|upgma|upgma_modified|nj|chained [seed]>   guide tree method (default sl)
 //   -gt_export                               write the guide tree in Newick format and stop
 //   -dist_export [-pid] [-square_matrix]     write the distance (or identity) matrix as CSV
@@ -27,6 +32,9 @@
 #include <vector>
 #include <unistd.h>
 
+#include <mutex>
+
+#include "batch.h"
 #include "pipeline.h"
 
 using namespace famsa_host;
@@ -53,6 +61,7 @@ bool find_option(std::vector<std::string>& p, const std::string& name, std::stri
 void usage()
 {
     std::cerr << "Usage: famsa-gpu [options] <input_file> <output_file>\n"
+                 "       famsa-gpu [tree options] -gt_export -batch <list_file>\n"
                  "  -gt <sl | slink | upgma | upgma_modified | nj | chained [seed]>  guide tree method (default: sl)\n"
                  "  -gt_export            export the guide tree to the output file in Newick format\n"
                  "  -dist_export          export the distance matrix to the output file in CSV format\n"
@@ -67,7 +76,27 @@ void usage()
                  "  -stats <file>         the run's statistics as \"[stats]\" + key=value lines (what -v prints)\n"
                  "  -gpu <id[,id...]>     HIP device(s) (default 0); -gpus <n> = devices 0..n-1.  With several devices\n"
                  "                        the all-pairs work is tiled by row blocks over them\n"
+                 "  -batch <list_file>    with -gt_export: guide trees for many inputs in one process; the list holds one\n"
+                 "                        \"input<TAB>output\" per line ('#' starts a comment line).  -v prints the batch's totals\n"
                  "  -t <n>, -v, -vv       accepted for compatibility / verbosity\n";
+}
+
+// the lines of a -batch list: (input, output) pairs
+std::vector<std::pair<std::string, std::string>> read_batch_list(const std::string& path)
+{
+    std::ifstream f(path);
+    if (!f.good()) throw std::runtime_error("cannot open the batch list " + path);
+    std::vector<std::pair<std::string, std::string>> out;
+    std::string line;
+    for (int number = 1; std::getline(f, line); ++number) {
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (line.find_first_not_of(" \t") == std::string::npos || line[0] == '#') continue;
+        const size_t tab = line.find('\t');
+        if (tab == std::string::npos || tab == 0 || tab + 1 >= line.size() || line.find('\t', tab + 1) != std::string::npos)
+            throw std::runtime_error(path + ": line " + std::to_string(number) + " is not \"input<TAB>output\"");
+        out.emplace_back(line.substr(0, tab), line.substr(tab + 1));
+    }
+    return out;
 }
 
 } // namespace
@@ -110,7 +139,9 @@ int main(int argc, char** argv)
         if (find_option(params, "-sample_size", aux)) opt.fast.sample_size = std::stoi(aux);
         if (find_option(params, "-num_evals", aux)) opt.fast.num_evaluations = std::stoi(aux);
         if (find_option(params, "-dump_seeds", aux)) opt.dump_seeds_path = aux;
-        std::string stats_path;
+        std::string stats_path, batch_list;
+        const bool batch = find_option(params, "-batch", batch_list);
+        if (!batch && find_switch(params, "-batch")) throw std::runtime_error("-batch needs a list file");
         (void)find_option(params, "-stats", stats_path);
         (void)find_option(params, "-shuffle", aux); // developer builds of the reference parse it; nothing consumes it
         if (find_option(params, "-cluster_fraction", aux)) opt.fast.cluster_fraction = std::stof(aux);
@@ -145,6 +176,72 @@ int main(int argc, char** argv)
         for (const char* unsupported : {"-gz", "-refine_mode", "-trim_columns", "-go", "-ge", "-r"})
             if (std::find(params.begin(), params.end(), unsupported) != params.end())
                 throw std::runtime_error(std::string(unsupported) + " is outside the scope of famsa-gpu (guide tree / distance stage only)");
+        if (batch) {
+            // refused before anything is started: what a batch does not cover
+            if (export_dist) throw std::runtime_error("-batch makes guide trees (-gt_export); it cannot be combined with -dist_export");
+            if (!stats_path.empty()) throw std::runtime_error("-batch cannot be combined with -stats (-v prints the batch's totals)");
+            if (!opt.dump_seeds_path.empty()) throw std::runtime_error("-batch cannot be combined with -dump_seeds (one seed file for many inputs)");
+            if (devices.size() != 1) throw std::runtime_error("-batch runs on one GPU; it cannot be combined with -gpus / several -gpu ids");
+            if (!params.empty())
+                throw std::runtime_error("-batch takes its inputs and outputs from the list file; unexpected argument: " + params[0]);
+            if (!export_tree) throw std::runtime_error("-batch needs -gt_export");
+            const auto list = read_batch_list(batch_list);
+            const auto clock_batch = std::chrono::steady_clock::now();
+            {
+                const int lanes = getenv("LCSGPU_LANES") ? atoi(getenv("LCSGPU_LANES")) : 16;
+                setenv("GPU_MAX_HW_QUEUES", std::to_string(std::max(1, std::min(lanes, 16))).c_str(), 0);
+            }
+            g_abandon_engine_at_return = getenv("FAMSA_GPU_CLEAN_EXIT") == nullptr;
+            int failed = 0;
+            BatchTotals totals;
+            double store_s = 0;
+            if (!list.empty()) {
+                EngineFuture engine = start_engine(devices, opt.heuristic != 0 ? fasttree_pool_threads(n_threads) : 0);
+                std::vector<BatchJob> jobs(list.size());
+                for (size_t i = 0; i < list.size(); ++i) {
+                    jobs[i].input = list[i].first;
+                    jobs[i].opt = opt;
+                }
+                std::mutex mu; // stderr, the counters
+                guide_trees_newick_gpu(jobs, devices[0], &totals, &engine, [&](size_t i, const BatchResult& r) {
+                    std::string problem = r.ok ? std::string() : r.message;
+                    double spent = 0;
+                    if (r.ok) {
+                        const auto c0 = std::chrono::steady_clock::now();
+                        std::ofstream f(list[i].second, std::ios::binary);
+                        if (!f.good()) problem = "cannot open " + list[i].second;
+                        else {
+                            f << r.newick;
+                            f.close();
+                            if (f.fail()) problem = "writing " + list[i].second + " failed (disk full?)";
+                        }
+                        spent = std::chrono::duration<double>(std::chrono::steady_clock::now() - c0).count();
+                    }
+                    std::lock_guard<std::mutex> lk(mu);
+                    store_s += spent;
+                    if (!problem.empty()) {
+                        ++failed;
+                        std::cerr << "[ERROR] " << list[i].first << ": " << problem << std::endl;
+                    }
+                });
+            }
+            if (verbose)
+                std::cerr << "batch.files=" << list.size() << "\nbatch.chunks=" << totals.chunks << "\nbatch.files_in_chunks=" << totals.in_chunks
+                          << "\nbatch.files_one_file_route=" << totals.one_file << "\nbatch.files_failed=" << failed
+                          << "\nbatch.group_max=" << batch_group_max() << "\nbatch.pair_budget=" << batch_pair_budget()
+                          << "\ntime.load=" << totals.load_s << "\ntime.sort=" << totals.sort_s << "\ntime.gpu_upload=" << totals.upload_s
+                          << "\ntime.device=" << totals.device_s << "\ntime.one_file_route=" << totals.one_file_s << "\ntime.newick=" << totals.newick_s
+                          << "\ntime.store=" << store_s << "\ntime.main_until_exit="
+                          << std::chrono::duration<double>(std::chrono::steady_clock::now() - clock_batch).count() << "\n";
+            const int code = failed ? 2 : 0;
+            if (!getenv("FAMSA_GPU_CLEAN_EXIT")) { // as below: the results are on disk
+                std::cerr.flush();
+                std::cout.flush();
+                fflush(nullptr);
+                _exit(code);
+            }
+            return code;
+        }
         if (params.size() != 2) {
             usage();
             return 1;

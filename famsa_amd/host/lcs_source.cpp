@@ -182,9 +182,10 @@ void GpuLcsSource::upload_records(const uint8_t* codes, const std::vector<uint64
         lens_[i] = (uint32_t)(offsets[r + 1] - offsets[r]);
     }
     wide_ = LcsSource::wide();
-    std::vector<uint8_t> flags(n ? n : 1);
-    int32_t nq = lcsgpu_orientation_flags(ctx_, flags.data());
+    flags_.assign(n ? n : 1, 0);
+    int32_t nq = lcsgpu_orientation_flags(ctx_, flags_.data());
     if (nq < 0) check(nq, "lcsgpu_orientation_flags");
+    flags_.resize(n);
     sensitive_ = nq > 0;
 }
 
@@ -293,6 +294,17 @@ bool GpuLcsSource::prim_edges(int distance_kind, std::vector<MstEdge>& edges, bo
     check(rc, "lcsgpu_mst_prim");
     add_kernel_ms(ctx_);
     return true;
+}
+
+void GpuLcsSource::prim_edges_batch(const int* ids, const int64_t* offsets, int n_groups, int distance_kind, bool triangle_orientation,
+                                    std::vector<MstEdge>& edges)
+{
+    size_t count = 0;
+    for (int g = 0; g < n_groups; ++g) count += offsets[g + 1] - offsets[g] > 1 ? (size_t)(offsets[g + 1] - offsets[g] - 1) : 0;
+    edges.resize(count);
+    const int flags = triangle_orientation ? LCSGPU_MST_TRIANGLE_ORIENTATION : 0;
+    check(lcsgpu_mst_prim_batch(ctx_, ids, offsets, n_groups, distance_kind | flags, (lcsgpu_mst_edge*)edges.data()), "lcsgpu_mst_prim_batch");
+    add_kernel_ms(ctx_);
 }
 
 bool GpuLcsSource::upgma_nodes(int distance_kind, bool modified, std::vector<int32_t>& left, std::vector<int32_t>& right)

@@ -24,7 +24,9 @@ namespace famsa_host {
 // pool instead of twice the cores: measurements), csv_input_order (-dist_export asks for its rectangles with the columns as
 // they were read instead of by length: measurements), leafmax=N (threads of that pool that may work on leaves while splits wait:
 // measurements), release_early / release_never / no_spare_tree / no_level_scratch (host memory of the tree heuristics as it was
-// before the second session of round 6: measurements).  Not read on any product default path.
+// before the second session of round 6: measurements), batch_pairs=N / batch_group_max=N (batch mode: the pair budget of a chunk and
+// the routing limit, batch.h -- tests force several chunks / the one-file route with them; unset, the defaults hold).  Not read on any
+// product default path beyond that.
 bool host_test(const char* name);
 int host_test_int(const char* key, int dflt);
 // LCSGPU_PROFILE: stage / call statistics on stderr (the library prints its own under the same switch)
@@ -62,6 +64,9 @@ public:
     virtual void rect(const int* refs, int n_refs, const int* cols, int n_cols, LcsBuf& out) = 0;
     // lower triangle over an id list: out[k*(k-1)/2 + c] = LCS(ref = ids[k], partner = ids[c]), c < k
     virtual void triangle_ids(const int* ids, int n_ids, LcsBuf& out);
+    // the source's sequences are a whole input set (not a leaf of the FastTree recursion) although its reducers run on the
+    // host: degenerate sets are refused as the device reducers of a whole set refuse them (trees.cpp, nj_tree)
+    virtual bool whole_input() const { return false; }
     // values need 32 bits (some sequence longer than 65535 residues); sources cache this
     virtual bool wide() const;
     // The whole lower triangle where the source already holds it in host memory (uint16, or uint32 if wide()):
@@ -134,6 +139,12 @@ public:
     void rect(const int* refs, int n_refs, const int* cols, int n_cols, LcsBuf& out) override;
     void triangle_ids(const int* ids, int n_ids, LcsBuf& out) override;
     bool prim_edges(int distance_kind, std::vector<MstEdge>& edges, bool triangle_orientation) override;
+    // Prim's MST of several id lists in one request (lcsgpu_mst_prim_batch on the first device): list g =
+    // ids[offsets[g] .. offsets[g + 1]), its max(m_g - 1, 0) records one list after the other, member numbers 0 .. m_g - 1
+    void prim_edges_batch(const int* ids, const int64_t* offsets, int n_groups, int distance_kind, bool triangle_orientation,
+                          std::vector<MstEdge>& edges);
+    // per uploaded sequence: 1 if it is orientation sensitive as a ref (lcsgpu_orientation_flags)
+    const std::vector<uint8_t>& orientation_flags() const { return flags_; }
     bool upgma_nodes(int distance_kind, bool modified, std::vector<int32_t>& left, std::vector<int32_t>& right) override;
     bool nj_nodes(int distance_kind, std::vector<int32_t>& left, std::vector<int32_t>& right) override;
     bool clarans(const int* ids, int n_ids, int distance_kind, int n_medoids, int n_fixed, float explore_fraction,
@@ -162,6 +173,7 @@ private:
     lcsgpu_ctx* ctx_ = nullptr; // = ctxs_[0]
     std::atomic<unsigned> next_{0};
     std::vector<uint32_t> lens_;
+    std::vector<uint8_t> flags_;
     bool sensitive_ = false, wide_ = false;
     double kernel_ms_ = 0;
     int text_slots_ = 0; // per context, between text_begin and text_end

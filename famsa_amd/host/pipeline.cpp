@@ -8,6 +8,7 @@
 
 #include <chrono>
 #include <cstdlib>
+#include <functional>
 #include <stdexcept>
 
 namespace famsa_host {
@@ -142,7 +143,15 @@ void release_in_background(Bytes& bytes)
 }
 
 std::string newick_gpu(const SeqSet& s, SeqSet* consumable, int device, const TreeOptions& opt, Timings* t, EngineFuture* engine);
+// the same once the engine is asked for: wait_for_engine() is called after the sort, where newick_gpu consumes its future
+std::string newick_on_engine(const SeqSet& s, SeqSet* consumable, const TreeOptions& opt, Timings* t,
+                             const std::function<GpuLcsSource&()>& wait_for_engine);
 } // namespace
+
+std::string guide_tree_newick_gpu(const SeqSet& s, GpuLcsSource& engine, const TreeOptions& opt, Timings* t)
+{
+    return newick_on_engine(s, nullptr, opt, t, [&engine]() -> GpuLcsSource& { return engine; });
+}
 
 std::string guide_tree_newick_gpu(const SeqSet& s, int device, const TreeOptions& opt, Timings* t, EngineFuture* engine)
 {
@@ -162,6 +171,18 @@ std::string newick_gpu(const SeqSet& s, SeqSet* consumable, int device, const Tr
         own = start_engine(device);
         engine = &own;
     }
+    std::unique_ptr<GpuLcsSource> held;
+    std::string nwk = newick_on_engine(s, consumable, opt, t, [&]() -> GpuLcsSource& {
+        held = engine->get(); // waits only for what the sort did not cover
+        return *held;
+    });
+    if (g_abandon_engine_at_return && !profile_on()) (void)held.release();
+    return nwk;
+}
+
+std::string newick_on_engine(const SeqSet& s, SeqSet* consumable, const TreeOptions& opt, Timings* t,
+                             const std::function<GpuLcsSource&()>& wait_for_engine)
+{
     double t0 = now_s();
     WorkSet w = make_workset(s, opt.keep_duplicates, opt.fast.n_threads);
     std::vector<int> in_of(w.n_unique());
@@ -175,8 +196,7 @@ std::string newick_gpu(const SeqSet& s, SeqSet* consumable, int device, const Tr
     const bool fast_tree = opt.heuristic != 0 && (int)s.size() >= opt.fast.threshold && w.n_unique() >= 2;
     if (fast_tree && w.n_unique() >= 100000 && !host_test("no_spare_tree"))
         spare_ready = std::async(std::launch::async, [&spare, n = (size_t)w.n_unique()] { spare.assign(2 * n - 1, node_t(-1, -1)); });
-    std::unique_ptr<GpuLcsSource> held = engine->get(); // waits only for what the sort did not cover
-    GpuLcsSource& src = *held;
+    GpuLcsSource& src = wait_for_engine();
     double t1b = now_s();
     src.upload_ordered(s.codes.data(), s.offsets, in_of); // the records as they were read; the engine gathers the working order's on the device
     if (spare_ready.valid()) spare_ready.get();
@@ -206,7 +226,6 @@ std::string newick_gpu(const SeqSet& s, SeqSet* consumable, int device, const Tr
         t->kernel_ms = src.kernel_ms_total();
         t->transport = src.transport();
     }
-    if (g_abandon_engine_at_return && !profile_on()) (void)held.release();
     return nwk;
 }
 } // namespace

@@ -48,6 +48,8 @@ EngineFuture start_engine(int device);
 EngineFuture start_engine(const std::vector<int>& devices, int expect_threads = 0); // one context per entry (entries may repeat)
 std::string guide_tree_newick_gpu(const SeqSet& s, int device, const TreeOptions& opt, Timings* t,
                                   EngineFuture* engine = nullptr);
+// The same on an engine the caller keeps (many inputs, one context: batch.h); the engine's uploaded set is replaced.
+std::string guide_tree_newick_gpu(const SeqSet& s, GpuLcsSource& engine, const TreeOptions& opt, Timings* t);
 // The same for a caller that does not need the residues afterwards: once the tree is built, `s.codes` is given back to
 // the system by a background thread while the Newick is made (at 3 x 10^6 records the process otherwise carries 0.8 GB
 // to its exit, and the exit takes that much longer).  Ids, offsets and lengths stay.

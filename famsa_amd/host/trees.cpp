@@ -704,7 +704,10 @@ void upgma_square(LcsSource&, tree_structure&) {}
 // the live clusters in ascending order of their rows, first strict minimum; the sums s are float accumulations whose order
 // is part of the result.  Here the live rows are a linked list in index order (the reference erases from a vector: the same
 // order), the sums live per row.
-void nj_tree(std::vector<float>& D, int n, tree_structure& tree)
+// refuse_degenerate: when no q is below FLT_MAX (a set whose pairs all have LCS 0) the reference keeps min_i = min_j = 0 and
+// its result is degenerate; the device reducer of a whole input (lcsgpu_nj) refuses such a set, and a source that stands
+// for a whole input (LcsSource::whole_input) has the host form refuse it in the same words.
+void nj_tree(std::vector<float>& D, int n, tree_structure& tree, bool refuse_degenerate = false)
 {
     std::vector<float> sum(n, 0.0f);
     std::vector<int> node(n), next(n + 1), prev(n + 1);
@@ -725,6 +728,8 @@ void nj_tree(std::vector<float>& D, int n, tree_structure& tree)
                 const float q = (live - 2) * D[tri(x, y)] - sum[x] - sum[y];
                 if (q < q_min) { q_min = q; a = x; b = y; }
             }
+        if (a == b && refuse_degenerate)
+            throw std::runtime_error("NJ: no finite q (a pair with LCS 0?) -- the reference's result is degenerate for this input");
         const float d_ab = D[tri(a, b)];
         tree.emplace_back(node[a], node[b]);
         node[a] = n + made; // the joined cluster keeps row a; row b leaves
@@ -777,7 +782,7 @@ void build_partial_d(LcsSource& src, GT method, tree_structure& tree)
         }
         std::vector<float> dist;
         float_triangle<D>(src, dist);
-        nj_tree(dist, n, tree);
+        nj_tree(dist, n, tree, src.whole_input());
         break;
     }
     default: throw std::runtime_error("not a partial generator");

@@ -31,6 +31,12 @@ class Host:
         lib.famsa_host_tree_gpu.restype = C.c_long
         lib.famsa_host_tree_gpu.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.c_int, C.c_int, *heur, C.c_char_p,
                                             C.c_long]
+        lib.famsa_host_trees_gpu.restype = C.c_long
+        lib.famsa_host_trees_gpu.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.c_int, C.c_int, *heur, C.c_char_p, C.c_long,
+                                             C.c_void_p, C.c_void_p]
+        lib.famsa_host_trees_message.restype = C.c_char_p
+        lib.famsa_host_trees_message.argtypes = [C.c_int]
+        lib.famsa_host_batch_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p]
         lib.famsa_host_dist_export_gpu.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p]
         lib.famsa_host_workset.argtypes = [C.c_char_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
         lib.famsa_host_format_distance.argtypes = [C.c_double, C.c_char_p]
@@ -83,6 +89,36 @@ class Host:
         return self._text(lambda buf: self.lib.famsa_host_tree_gpu(
             fasta.encode(), device, method.encode(), DIST[distance], int(keep_duplicates), self.HEUR[heuristic],
             subtree_size, sample_size, threshold, cluster_fraction, cluster_iters, buf, len(buf)))
+
+    def trees_gpu(self, fastas, method, distance="indel075_div_lcs", keep_duplicates=False, device=0, heuristic=None,
+                  subtree_size=0, sample_size=0, threshold=0, cluster_fraction=0.0, cluster_iters=0):
+        """Guide trees of many files on one engine context: a list with the Newick bytes of a file or, where the file
+        failed, a RuntimeError with its message."""
+        n = len(fastas)
+        paths = (C.c_char_p * max(n, 1))(*[f.encode() for f in fastas])
+        offsets = np.zeros(n + 1, np.int64)
+        status = np.zeros(max(n, 1), np.int32)
+        cap = 4096
+        for f in fastas:
+            cap += 64 + (4 * os.path.getsize(f) if os.path.isfile(f) else 0)
+        text = self._text(lambda buf: self.lib.famsa_host_trees_gpu(
+            C.cast(paths, C.c_void_p), n, device, method.encode(), DIST[distance], int(keep_duplicates), self.HEUR[heuristic],
+            subtree_size, sample_size, threshold, cluster_fraction, cluster_iters, buf, len(buf), offsets.ctypes.data,
+            status.ctypes.data), cap=cap)
+        return [text[int(offsets[i]):int(offsets[i + 1])] if status[i] == 0
+                else RuntimeError(self.lib.famsa_host_trees_message(i).decode(errors="replace")) for i in range(n)]
+
+    def batch_plan(self, unique_counts, eligible, pair_budget=0, group_max=0):
+        """The batch's chunk planner (no GPU): (chunk number per file, -1 = the one-file route; number of chunks)."""
+        counts = np.ascontiguousarray(unique_counts, np.int64)
+        flags = np.ascontiguousarray(eligible, np.uint8)
+        assert len(counts) == len(flags)
+        plan = np.zeros(max(len(counts), 1), np.int32)
+        chunks = self.lib.famsa_host_batch_plan(counts.ctypes.data, flags.ctypes.data, len(counts), int(pair_budget), int(group_max),
+                                                plan.ctypes.data)
+        if chunks < 0:
+            raise self._err()
+        return plan[: len(counts)].copy(), chunks
 
     def dist_export_gpu(self, fasta, path, distance="indel075_div_lcs", square_matrix=False, pid=False, device=0):
         if self.lib.famsa_host_dist_export_gpu(fasta.encode(), device, DIST[distance], int(square_matrix), int(pid),
@@ -156,6 +192,23 @@ def guide_tree(fasta, gt="sl", distance="indel075_div_lcs", keep_duplicates=Fals
     heuristic: None, "medoidtree" or "parttree" (keyword arguments subtree_size, sample_size, threshold,
     cluster_fraction, cluster_iters as in FAMSA)."""
     return _host().tree_gpu(fasta, gt, distance, keep_duplicates, device, heuristic, **medoid)
+
+
+def guide_trees(fastas, gt="sl", distance="indel075_div_lcs", keep_duplicates=False, heuristic=None, device=0, on_error="raise",
+                **medoid):
+    """guide_tree for many files in ONE process on ONE engine context: a list with the Newick text (bytes) of every file, each
+    what guide_tree gives for that file alone.  Families up to the routing limit are made together, chunk by chunk (one
+    workgroup per family for -gt sl / slink; the host builders over batched triangles for upgma / upgma_modified / nj); the
+    rest goes through the one-file path on the same context.  A file that fails does not stop the others: on_error="raise"
+    raises the first failure after all files are done, on_error="return" puts the exception into that file's slot."""
+    if on_error not in ("raise", "return"):
+        raise ValueError("on_error must be 'raise' or 'return'")
+    out = _host().trees_gpu(list(fastas), gt, distance, keep_duplicates, device, heuristic, **medoid)
+    if on_error == "raise":
+        for r in out:
+            if isinstance(r, Exception):
+                raise r
+    return out
 
 
 def dist_export(fasta, csv_path, distance="indel075_div_lcs", square_matrix=False, pid=False, device=0):

@@ -55,6 +55,7 @@ def load_library():
         "lcsgpu_lcs_triangle_ids": (C.c_int, [vp, pi32, i32, vp, C.c_int]),
         "lcsgpu_row_minima_dev": (C.c_int, [vp, vp, C.c_int, i32, i32, C.c_int, vp, C.c_int]),
         "lcsgpu_mst_prim": (C.c_int, [vp, C.c_int, vp]),
+        "lcsgpu_mst_prim_batch": (C.c_int, [vp, pi32, C.POINTER(C.c_int64), i32, C.c_int, vp]),
         "lcsgpu_mst_shard_begin": (C.c_int, [vp, vp, C.c_int, i32, i32, C.c_int]),
         "lcsgpu_mst_shard_best": (C.c_int, [vp, vp, vp]),
         "lcsgpu_mst_shard_merge": (C.c_int, [vp, vp, i32, pi32]),
@@ -97,6 +98,7 @@ def load_library():
 MST_EDGE = np.dtype([("from", np.int32), ("to", np.int32), ("dist", np.float64)])  # lcsgpu_mst_edge
 MST_KEY = np.dtype([("dist_bits", np.uint64), ("id", np.uint64)])                  # lcsgpu_mst_key
 MST_TRIANGLE_ORIENTATION = 0x100
+MST_BATCH_MAX_MEMBERS = 4096  # lcsgpu_mst_prim_batch: members of one group at most
 MST_COMPUTE = 0x200  # lcsgpu_mst_shard_begin: the LCS launch itself does the local half (see include/lcsgpu.h)
 
 
@@ -263,6 +265,27 @@ class LcsGpu:
         out = np.zeros(max(self.n - 1, 0), dtype=MST_EDGE)
         self._check(self._lib.lcsgpu_mst_prim(self._ctx, kind, out.ctypes.data if out.size else None))
         return out
+
+    def mst_prim_batch(self, groups, kind=1, triangle_orientation=False, out=None):
+        """Prim's MST of several id lists of the uploaded set, one call (lcsgpu_mst_prim_batch): per list what mst_prim
+        returns for that list uploaded alone in list order (member numbers, insertion order from member 0).  Returns a
+        list of MST_EDGE arrays.  out (optional): the flat MST_EDGE array the library writes into, sum of max(m - 1, 0)
+        records at least -- the returned arrays are then views of it."""
+        sizes = [len(g) for g in groups]
+        offs = np.zeros(len(groups) + 1, dtype=np.int64)
+        np.cumsum(sizes, out=offs[1:])
+        ids = np.ascontiguousarray(np.concatenate([np.asarray(g, np.int32) for g in groups])
+                                   if offs[-1] else np.zeros(0, np.int32), dtype=np.int32)
+        base = np.zeros(len(groups) + 1, dtype=np.int64)
+        np.cumsum([max(m - 1, 0) for m in sizes], out=base[1:])
+        if out is None:
+            out = np.zeros(max(int(base[-1]), 1), dtype=MST_EDGE)
+        assert out.dtype == MST_EDGE and out.flags.c_contiguous and len(out) >= int(base[-1])
+        self._check(self._lib.lcsgpu_mst_prim_batch(self._ctx, ids.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                    offs.ctypes.data_as(C.POINTER(C.c_int64)), len(groups),
+                                                    int(kind) | (MST_TRIANGLE_ORIENTATION if triangle_orientation else 0),
+                                                    out.ctypes.data))
+        return [out[base[g]:base[g + 1]] for g in range(len(groups))]
 
     # ---- sharded MST (Boruvka over row blocks; one context per GPU) ----
     def mst_shard_begin(self, d_tri_ptr, elem_size, row_begin, row_end, kind=1):

@@ -357,6 +357,25 @@ int lcsgpu_multi_transport(lcsgpu_ctx* const* ctxs, int32_t n_ctx, char* buf, si
 int lcsgpu_lcs_triangles_batch(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* group_offsets, int32_t n_groups,
                                void* out, int elem_size);
 
+/* Prim's MST of several id lists in one call (the guide trees of many small families): list g =
+ * ids[group_offsets[g] .. group_offsets[g+1]), m_g members, any ids of the uploaded set in any order.
+ * out_edges (HOST) receives list g's max(m_g - 1, 0) records at record offset sum_{h<g} max(m_h - 1, 0):
+ * exactly what lcsgpu_mst_prim returns for that list uploaded alone in list order -- from < to are MEMBER
+ * numbers 0 .. m_g - 1, the order is Prim's insertion order from member 0, keys are
+ * (d, ~pack(min, max)) compared lexicographically, d = Transform<double, kind> with the host-filled pow
+ * table and IEEE double division (lcs == 0: nextafter(DBL_MAX, 0)).  The lists' triangles are computed as
+ * by lcsgpu_lcs_triangles_batch (ref = the LATER member of the list) and stay on the device; then ONE
+ * launch runs every list's recurrence in a workgroup of its own.
+ * distance_kind may carry LCSGPU_MST_TRIANGLE_ORIENTATION.
+ * LCSGPU_E_UNSUPPORTED (nothing computed, out_edges untouched): a list of more than
+ * LCSGPU_MST_BATCH_MAX_MEMBERS members; a named sequence longer than 65535 residues; a named sequence that
+ * is orientation sensitive while LCSGPU_MST_TRIANGLE_ORIENTATION is not set (MSTPrim wants LCS(ref = the
+ * node just added), which a triangle does not hold) -- lcsgpu_mst_prim on the list uploaded alone applies.
+ * Replaces: MSTPrim::run_view (tree/MSTPrim.cpp:356-533), once per list. */
+#define LCSGPU_MST_BATCH_MAX_MEMBERS 4096
+int lcsgpu_mst_prim_batch(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* group_offsets, int32_t n_groups,
+                          int distance_kind, lcsgpu_mst_edge* out_edges);
+
 /* Seed assignment of one FastTree evaluation: for r = 0 .. n_seeds-1 in order,
  *   d = Transform<float>(LCS(ref = seed_ids[r], partner = col_ids[j]));  if (d < dist[j]) { dist[j] = d; assign[j] = first_k + r; }
  * dist / assign (HOST, n_cols entries each) are read and updated: the caller initialises them with the

@@ -1,0 +1,223 @@
+#!/usr/bin/env python3
+"""Batch mode against the two ways there were before it, on families of 50 / 200 / 1000 / 4000 members (an ancestor of
+60-400 aa, 20 % substitutions per member, lengths cut to 90-100 % of it, as mst_shapes._ragged4 makes them; fixed seed):
+512 / 512 / 128 / 16 FASTA files in a temporary directory, -gt sl and -gt upgma, as files per second:
+  (a) one famsa-gpu process per file -- the only command-line route before, the baseline;
+  (b) a loop over famsa_amd.guide_tree in one process -- the best there was;
+  (c) famsa-gpu -batch over the whole directory;
+  (c1) the same with FAMSA_HOST_TEST=batch_group_max=1: every file down the one-file route, but on the batch's ONE engine
+       context -- what separates the routing (a workgroup per family against lcsgpu_mst_prim's rounds per file) from what
+       the shared context and the parallel loading give on their own.  The routing limit is the largest size at which (c)
+       is not behind (c1).
+(a) and (b) cost a process start or an engine context per file, so they are timed on the first --files-a / --files-b files
+of a size (a rate does not need all 512); (c) takes all of them.  Medians of --reps timed runs after one warm-up.
+
+Before that, the kernel's own part (engine level, one process per setting of LCSGPU_TUNE=mst_batch_square): for one group
+of m members, lcsgpu_mst_prim on the group uploaded alone against lcsgpu_mst_prim_batch on it -- wall time of the call and
+the kernels' time (for the batch: its launches minus those of lcsgpu_lcs_triangles_batch on the same group = the Prim
+launch, with the square's expansion where that is on) -- with the packed triangle read as it is and with the expanded
+square.  (One group alone is the kernel's worst case: what it is for is many groups side by side, the `many` column.)
+
+Writes everything to stdout and to --out (default profiles/batch_trees.txt)."""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np  # noqa: E402
+
+SIZES = (50, 200, 1000, 4000)
+COUNTS = (512, 512, 128, 16)
+ALPHABET = "ARNDCQEGHILKMFPSTWYV"
+
+
+def family(rng, members):
+    length = int(rng.integers(60, 401))
+    anc = rng.integers(0, 20, size=length, dtype=np.uint8)
+    out = []
+    for _ in range(members):
+        s = anc.copy()
+        m = rng.random(length) < 0.2
+        s[m] = rng.integers(0, 20, size=int(m.sum()), dtype=np.uint8)
+        out.append(s[: int(rng.integers(int(length * 0.9), length + 1))])
+    return out
+
+
+def write_fasta(path, seqs):
+    letters = np.frombuffer(ALPHABET.encode(), np.uint8)
+    with open(path, "wb") as f:
+        for i, s in enumerate(seqs):
+            f.write(b">s%d\n" % i + letters[s].tobytes() + b"\n")
+
+
+def median_of(fn, reps):
+    fn()  # warm-up
+    times = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        times.append(time.perf_counter() - t0)
+    return statistics.median(times)
+
+
+def kernel_child(sizes, reps):
+    """Runs in a child per LCSGPU_TUNE setting: one JSON line per group size."""
+    import famsa_amd
+    rng = np.random.Generator(np.random.PCG64(77))
+    eng = famsa_amd.LcsGpu(0)
+    for m in sizes:
+        seqs = family(rng, m)
+        eng.upload_seqs(seqs)
+        group = [np.arange(m, dtype=np.int32)]
+        rec = {"m": m}
+        for name, call in (("mst_prim", lambda: eng.mst_prim(1)), ("batch", lambda: eng.mst_prim_batch(group, 1)),
+                           ("triangles", lambda: eng.lcs_triangles_batch(group))):
+            call()
+            wall, ms = [], []
+            for _ in range(reps):
+                t0 = time.perf_counter()
+                call()
+                wall.append(time.perf_counter() - t0)
+                ms.append(eng.last_kernel_ms()[0])
+            rec[name + "_wall_ms"] = 1e3 * statistics.median(wall)
+            rec[name + "_kernel_ms"] = statistics.median(ms)
+        # many groups of this size side by side: what a chunk looks like to the device
+        many = max(1, min(64, 16384 // m))
+        groups = [np.arange(m, dtype=np.int32)] * many
+        eng.mst_prim_batch(groups, 1)
+        wall = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            eng.mst_prim_batch(groups, 1)
+            wall.append(time.perf_counter() - t0)
+        rec["many"] = many
+        rec["many_wall_ms"] = 1e3 * statistics.median(wall)
+        print(json.dumps(rec), flush=True)
+    eng.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batch_trees.txt"))
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--files-a", type=int, default=8)
+    ap.add_argument("--files-b", type=int, default=16)
+    ap.add_argument("--scale", type=float, default=1.0, help="fraction of the 512 / 512 / 128 / 16 files to make")
+    ap.add_argument("--kernel-sizes", default="50,200,256,500,1000,1500,2000,3000,4096")
+    ap.add_argument("--skip-e2e", action="store_true")
+    ap.add_argument("--kernel-child", action="store_true", help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    ksizes = [int(x) for x in args.kernel_sizes.split(",") if x]
+    if args.kernel_child:
+        kernel_child(ksizes, args.reps)
+        return
+
+    lines = []
+
+    def say(text=""):
+        print(text, flush=True)
+        lines.append(text)
+        os.makedirs(os.path.dirname(args.out), exist_ok=True)
+        with open(args.out, "w") as f:  # (rewritten line by line: a run that is cut short leaves what it had)
+            f.write("\n".join(lines) + "\n")
+
+    say("# scripts/batch_trees_bench.py: medians of %d timed runs after one warm-up" % args.reps)
+    say()
+    say("## one group of m members in one process: lcsgpu_mst_prim (uploaded alone) against lcsgpu_mst_prim_batch")
+    say("## wall = the call, kernels = its launches; prim = batch kernels - lcsgpu_lcs_triangles_batch kernels (the Prim launch")
+    say("## and, with the square, its expansion); many = that many groups of m in one call, wall per group")
+    for square in (0, 1):
+        say("# LCSGPU_TUNE=mst_batch_square=%d (%s)" % (square, "the expanded m x m square" if square else "the packed triangle as it is"))
+        say("%6s %14s %14s %14s %14s %12s %16s" % ("m", "mst_prim wall", "mst_prim kern", "batch wall", "batch kern", "prim kern", "many: wall/group"))
+        env = dict(os.environ)
+        env["LCSGPU_TUNE"] = "mst_batch_square=%d" % square
+        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--kernel-child", "--reps", str(args.reps), "--kernel-sizes",
+                            args.kernel_sizes], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        if p.returncode != 0:
+            say("FAILED: " + p.stderr[-1500:])
+            return 1
+        for l in p.stdout.splitlines():
+            r = json.loads(l)
+            say("%6d %11.3f ms %11.3f ms %11.3f ms %11.3f ms %9.3f ms %10.3f ms x%d" % (
+                r["m"], r["mst_prim_wall_ms"], r["mst_prim_kernel_ms"], r["batch_wall_ms"], r["batch_kernel_ms"],
+                r["batch_kernel_ms"] - r["triangles_kernel_ms"], r["many_wall_ms"] / r["many"], r["many"]))
+        say()
+    if args.skip_e2e:
+        return 0
+
+    import famsa_amd
+    from famsa_amd.hostlib import CLI
+    rng = np.random.Generator(np.random.PCG64(2024))
+    with tempfile.TemporaryDirectory() as tmp:
+        files = {}
+        for m, count in zip(SIZES, COUNTS):
+            count = max(1, int(round(count * args.scale)))
+            files[m] = []
+            for k in range(count):
+                path = os.path.join(tmp, "f%d_%04d.fasta" % (m, k))
+                write_fasta(path, family(rng, m))
+                files[m].append(path)
+        out_dir = os.path.join(tmp, "out")
+        os.makedirs(out_dir)
+
+        def outs(paths):
+            return [os.path.join(out_dir, os.path.basename(p) + ".dnd") for p in paths]
+
+        say("## files per second; (a) one famsa-gpu process per file (first %d files), (b) famsa_amd.guide_tree in a loop in one" % args.files_a)
+        say("## process (first %d files), (c) famsa-gpu -batch (all files of the size)" % args.files_b)
+        say("## (c1) = (c) with every file sent down the one-file route on the batch's one engine context; (c4096) = (c) with the routing")
+        say("## limit at the kernel's cap: the chunks take every size")
+        say("%6s %6s %8s %12s %12s %12s %12s %14s %8s %8s" % ("gt", "m", "files", "(a) files/s", "(b) files/s", "(c) files/s", "(c1) files/s",
+                                                          "(c4096) files/s", "c / a", "c / b"))
+        for gt in ("sl", "upgma"):
+            for m in SIZES:
+                fa, fb, fc = files[m][: args.files_a], files[m][: args.files_b], files[m]
+
+                def run_a():
+                    for src, dst in zip(fa, outs(fa)):
+                        subprocess.run([CLI, "-gt", gt, "-gt_export", src, dst], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+
+                def run_b():
+                    for src in fb:
+                        famsa_amd.guide_tree(src, gt=gt)
+
+                lst = os.path.join(tmp, "list_%d.txt" % m)
+                with open(lst, "w") as f:
+                    for src, dst in zip(fc, outs(fc)):
+                        f.write("%s\t%s\n" % (src, dst))
+
+                def run_c(hook=None):
+                    env = dict(os.environ)
+                    env.pop("FAMSA_HOST_TEST", None)
+                    if hook:
+                        env["FAMSA_HOST_TEST"] = hook
+                    subprocess.run([CLI, "-gt", gt, "-gt_export", "-batch", lst], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL,
+                                   env=env)
+
+                a = len(fa) / median_of(run_a, args.reps)
+                b = len(fb) / median_of(run_b, args.reps)
+                c = len(fc) / median_of(run_c, args.reps)
+                c1 = len(fc) / median_of(lambda: run_c("batch_group_max=1"), args.reps)
+                c4096 = len(fc) / median_of(lambda: run_c("batch_group_max=4096"), args.reps)
+                say("%6s %6d %8d %12.1f %12.1f %12.1f %12.1f %14.1f %8.1f %8.1f" % (gt, m, len(fc), a, b, c, c1, c4096, c / a, c / b))
+                # the batch's outputs are the one-file command's (spot check on the files (a) wrote last)
+                run_a()
+                one = [open(p, "rb").read() for p in outs(fa)]
+                run_c()
+                assert one == [open(p, "rb").read() for p in outs(fa)], (gt, m)
+        p = subprocess.run([CLI, "-gt", "sl", "-gt_export", "-batch", lst, "-v"], stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True)
+        say()
+        say("## famsa-gpu -gt sl -gt_export -batch -v on the m = %d list" % SIZES[-1])
+        for l in p.stderr.splitlines():
+            say(l)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -22,6 +22,12 @@ int tune_int(const char* key, int dflt)
     return dflt;
 }
 
+void trace_lcs_launch(int bv, bool quirk, const lcsgpu::RowsArgs& a, long wgs)
+{
+    if (!tune_int("lcs_plan_trace", 0)) return; // (not cached: tests switch it inside one process)
+    fprintf(stderr, "lcsgpu: lcs launch h=%d quirk=%d fused=%d refs_per_wg=%d threads=%d wgs=%ld\n", bv, quirk ? 1 : 0,
+            a.fuse.on ? 1 : 0, (int)a.refs_per_block, a.block_threads == 64 ? 64 : 256, wgs);
+}
 
 int fail(int code, const char* fmt, ...)
 {
@@ -372,11 +378,13 @@ int run_rows(lcsgpu_ctx* ctx, Lane& L, int mode, const int32_t* ref_ids, int32_t
             const int total = tri_prefix[b].back();
             if (total > 0) {
                 HIP_TRY(lcsgpu::launch_rows(bk.bv, bk.quirk, a, total, 1, st));
+                trace_lcs_launch(bk.bv, bk.quirk, a, total);
                 ++L.last_launches;
             }
         } else if (bk.bv != 0) {
             if (gy > 65535) return fail(LCSGPU_E_INVALID, "too many ref tiles in one call (%d)", gy);
             HIP_TRY(lcsgpu::launch_rows(bk.bv, bk.quirk, a, gx, gy, st));
+            trace_lcs_launch(bk.bv, bk.quirk, a, (long)gx * gy);
             ++L.last_launches;
         } else {
             // long refs: slices of ref blocks so the carry scratch stays bounded
@@ -398,6 +406,7 @@ int run_rows(lcsgpu_ctx* ctx, Lane& L, int mode, const int32_t* ref_ids, int32_t
                 }
                 const int sgy = (s.n_refs + s.refs_per_block - 1) / s.refs_per_block;
                 HIP_TRY(lcsgpu::launch_long(bk.quirk, s, gx, sgy, L.d_carry.p, n_chunks_max, L.stream));
+                trace_lcs_launch(0, bk.quirk, s, (long)gx * sgy);
                 ++L.last_launches;
             }
         }

@@ -214,6 +214,7 @@ static int batch_triangles_to_device(lcsgpu_ctx* ctx, Lane& L, const int32_t* id
         a.refs_per_block = b.refs_per_wg;
         a.block_threads = b.narrow ? 64 : 0;
         HIP_TRY(lcsgpu::launch_rows(b.bv, b.quirk, a, (int)b.jobs.size(), 1, run_stream));
+        trace_lcs_launch(b.bv, b.quirk, a, (long)b.jobs.size());
         ++L.last_launches;
     }
     HIP_TRY(hipEventRecord(L.ev_stop, run_stream));
@@ -653,6 +654,7 @@ int lcsgpu_assign_seeds_batch(lcsgpu_ctx* ctx, const int32_t* seed_ids, const in
             a.mode = lcsgpu::MODE_RECT;
             a.refs_per_block = b.refs_per_wg;
             HIP_TRY(lcsgpu::launch_rows(b.bv, b.quirk, a, (int)b.jobs.size(), 1, L.stream));
+            trace_lcs_launch(b.bv, b.quirk, a, (long)b.jobs.size());
             ++L.last_launches;
         }
         HIP_TRY(hipEventRecord(L.ev_stop, L.stream));

@@ -34,8 +34,12 @@ int fail(int code, const char* fmt, ...);
 // for the chains of clarans_large_chain_kernel, where it is on by default: 250000), clarans_draws (step positions
 // drawn for a sample shape before its first launch, 65536), assign_batch_kb (LCS rectangles of one launch of the batched seed
 // assignment, 2 GB), upgma_spare (spare slots of the UPGMA matrix, n / 10), mst_batch_square (1, the default: lcsgpu_mst_prim_batch
-// expands every group's triangle to a square first; 0: it reads the packed triangles -- measurements)
+// expands every group's triangle to a square first; 0: it reads the packed triangles -- measurements), lcs_plan_trace (1: every
+// LCS launch is named on stderr with the plan it got -- a test aid, read at every call)
 int tune_int(const char* key, int dflt);
+// LCSGPU_TUNE lcs_plan_trace=1: one line per LCS launch, "lcsgpu: lcs launch h=<half-words, 0 = the long kernel> quirk=<0|1>
+// fused=<0|1> refs_per_wg=<R> threads=<64|256> wgs=<workgroups>"; nothing otherwise.  Called where a planner has launched.
+void trace_lcs_launch(int bv, bool quirk, const lcsgpu::RowsArgs& a, long wgs);
 
 #define HIP_TRY(expr)                                                                           \
     do {                                                                                        \

@@ -64,4 +64,34 @@ struct GroupPrimArgs {
 };
 hipError_t launch_group_prim(const GroupPrimArgs& a, hipStream_t stream);
 
+// ---- UPGMA of many small groups: one workgroup per group (upgma_group_kernels.hip) ----
+constexpr int UPGMA_GROUP_MAX_MEMBERS = MST_GROUP_MAX_MEMBERS; // = LCSGPU_UPGMA_BATCH_MAX_MEMBERS
+struct GroupUpgmaJob {
+    int64_t tri0;  // element offset of the group's packed LCS triangle in the launch's triangle buffer
+    int64_t sq0;   // ... of its m x m float square in the launch's square buffer
+    int64_t node0; // record offset of its m - 1 internal nodes
+    int32_t id0;   // position of its first member in the concatenated id list
+    int32_t m;     // members, 2 .. UPGMA_GROUP_MAX_MEMBERS
+    int32_t group; // the caller's list number: where its status goes
+    int32_t pad;
+};
+struct GroupUpgmaArgs {
+    const uint16_t* tri;       // the groups' packed triangles (ref = the later member)
+    float* sq;                 // the launch's squares
+    const GroupUpgmaJob* jobs; // the launch's jobs, longest first
+    const int64_t* row0;       // [n_jobs + 1] prefix sums of m over the launch's jobs
+    const int32_t* ids;        // the concatenated id lists
+    const uint32_t* lens;
+    const float* pow_f32;      // (float) pow(i, 0.75)
+    float* row_min;            // [total_rows] every row's initial key: distance,
+    int32_t* row_near;         //              and column
+    int32_t* left;
+    int32_t* right;
+    int32_t* status;           // [the call's groups] 1 = no finite nearest neighbour; zeroed before the launch
+    int64_t total_rows;        // row0[n_jobs]
+    int32_t n_jobs, kind, modified, max_m;
+};
+// the launch pair of a slice: the squares with the rows' initial keys, then the merges
+hipError_t launch_group_upgma(const GroupUpgmaArgs& a, hipStream_t stream);
+
 } // namespace lcsgpu

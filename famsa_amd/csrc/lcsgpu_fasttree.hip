@@ -409,6 +409,160 @@ int lcsgpu_mst_prim_batch(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* gr
     }
 }
 
+// UPGMA of many id lists: the lists' triangles by the launches of lcsgpu_lcs_triangles_batch, then per slice of lists a
+// launch pair (upgma_group_kernels.hip): the float squares with the rows' initial keys, and a workgroup per list that runs
+// the list's merges, longest lists first.
+static int upgma_batch_impl(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* group_offsets, int32_t n_groups, int distance_kind,
+                            int modified, int32_t* out_left, int32_t* out_right, int32_t* out_status)
+{
+    if (!ctx) return fail(LCSGPU_E_INVALID, "NULL ctx");
+    if (ctx->n < 0) return fail(LCSGPU_E_STATE, "no sequence set uploaded");
+    if (distance_kind != LCSGPU_DIST_INDEL_DIV_LCS && distance_kind != LCSGPU_DIST_INDEL075_DIV_LCS)
+        return fail(LCSGPU_E_INVALID, "unknown distance kind %d", distance_kind);
+    if (n_groups < 0 || (n_groups > 0 && !group_offsets)) return fail(LCSGPU_E_INVALID, "bad group table");
+    if (n_groups == 0) return LCSGPU_OK;
+    if (group_offsets[0] != 0) return fail(LCSGPU_E_INVALID, "group_offsets[0] must be 0");
+    const int64_t n_total = group_offsets[n_groups];
+    if (n_total < 0 || n_total > 0x7fffffff) return fail(LCSGPU_E_INVALID, "bad total id count");
+    if (n_total > 0 && !ids) return fail(LCSGPU_E_INVALID, "NULL ids");
+    // everything that refuses comes first: nothing is computed, the outputs stay as they are
+    std::vector<lcsgpu::GroupUpgmaJob> jobs;
+    int64_t n_nodes = 0;
+    for (int32_t g = 0; g < n_groups; ++g) {
+        const int64_t m = group_offsets[g + 1] - group_offsets[g];
+        if (m < 0) return fail(LCSGPU_E_INVALID, "group_offsets not ascending");
+        if (m > LCSGPU_UPGMA_BATCH_MAX_MEMBERS)
+            return fail(LCSGPU_E_UNSUPPORTED, "group %d has %lld members: the batched UPGMA handles at most %d (use lcsgpu_upgma)", g,
+                        (long long)m, LCSGPU_UPGMA_BATCH_MAX_MEMBERS);
+        if (m >= 2) {
+            jobs.push_back(lcsgpu::GroupUpgmaJob{(int64_t)g /* the group, until its triangle's place is known */, 0, n_nodes,
+                                                 (int32_t)group_offsets[g], (int32_t)m, g, 0});
+            n_nodes += m - 1;
+        }
+    }
+    for (int64_t p = 0; p < n_total; ++p) {
+        const int32_t id = ids[p];
+        if (id < 0 || id >= ctx->n) return fail(LCSGPU_E_INVALID, "id %d out of range", id);
+        if (ctx->lens[(size_t)id] > 65535)
+            return fail(LCSGPU_E_UNSUPPORTED, "sequence %d is longer than 65535 residues: the batched UPGMA keeps 16-bit LCS values", id);
+        // (orientation-sensitive members are served: the triangle's orientation, ref = the later member, IS
+        // UPGMA::computeDistances's)
+    }
+    if (!out_status) return fail(LCSGPU_E_INVALID, "NULL out_status");
+    if (n_nodes > 0 && (!out_left || !out_right)) return fail(LCSGPU_E_INVALID, "NULL out_left / out_right");
+    if (jobs.empty()) {
+        std::fill(out_status, out_status + n_groups, 0);
+        return LCSGPU_OK;
+    }
+    // the float squares of a launch pair: at most this many MB (a slice always holds at least one group)
+    static const int slice_mb = std::max(1, tune_int("upgma_group_mb", 4096));
+
+    LaneGuard guard(ctx, LaneGuard::ANY);
+    Lane& L = guard.lane();
+    std::vector<int64_t> tri_base;
+    int64_t count = 0;
+    bool had_long = false;
+    struct Shared { // from the first launch until the kernels have run (lcsgpu_lcs_triangles_batch)
+        ComputeGate& g;
+        bool held = false;
+        ~Shared() { if (held) g.unlock_shared(); }
+    } hold{ctx->gate};
+    int rc = batch_triangles_to_device(ctx, L, ids, group_offsets, n_groups, 2, tri_base, &count, &had_long, [&] {
+        hold.g.lock_shared();
+        hold.held = true;
+    });
+    if (rc) return rc;
+    if (count <= 0) return fail(LCSGPU_E_STATE, "the batched UPGMA found no pair to compute");
+    // longest first: the groups that take the most steps start first
+    std::stable_sort(jobs.begin(), jobs.end(), [](const lcsgpu::GroupUpgmaJob& x, const lcsgpu::GroupUpgmaJob& y) { return x.m > y.m; });
+    struct Slice { size_t job0, n_jobs, row_at; int64_t rows, sq_elems; int32_t max_m; };
+    std::vector<Slice> slices;
+    std::vector<int64_t> row0; // per slice: the prefix sums of m over its jobs, one slice after the other
+    const int64_t slice_elems = (int64_t)slice_mb * (1 << 20) / 4;
+    int64_t max_sq = 0, max_rows = 0;
+    for (size_t j = 0; j < jobs.size(); ++j) {
+        lcsgpu::GroupUpgmaJob& job = jobs[j];
+        job.tri0 = tri_base[(size_t)job.tri0];
+        const int64_t sq = (int64_t)job.m * job.m;
+        if (slices.empty() || slices.back().sq_elems + sq > slice_elems) {
+            slices.push_back(Slice{j, 0, row0.size(), 0, 0, job.m});
+            row0.push_back(0);
+        }
+        Slice& s = slices.back();
+        job.sq0 = s.sq_elems;
+        s.sq_elems += sq;
+        s.rows += job.m;
+        ++s.n_jobs;
+        row0.push_back(s.rows);
+        max_sq = std::max(max_sq, s.sq_elems);
+        max_rows = std::max(max_rows, s.rows);
+    }
+    auto a256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t o_jobs = 0, o_row0 = o_jobs + a256(jobs.size() * sizeof(lcsgpu::GroupUpgmaJob)), o_ids = o_row0 + a256(row0.size() * 8),
+                 o_left = o_ids + a256((size_t)n_total * 4), o_right = o_left + a256((size_t)n_nodes * 4),
+                 o_status = o_right + a256((size_t)n_nodes * 4), o_min = o_status + a256((size_t)n_groups * 4),
+                 o_near = o_min + a256((size_t)max_rows * 4), o_sq = o_near + a256((size_t)max_rows * 4),
+                 total = o_sq + a256((size_t)max_sq * 4);
+    rc = reserve_big(ctx, L.d_work, total, "the batched UPGMA's tables and squares");
+    if (rc) return rc;
+    char* base = (char*)L.d_work.p;
+    HIP_TRY(hipMemcpyAsync(base + o_jobs, jobs.data(), jobs.size() * sizeof(lcsgpu::GroupUpgmaJob), hipMemcpyHostToDevice, L.stream));
+    HIP_TRY(hipMemcpyAsync(base + o_row0, row0.data(), row0.size() * 8, hipMemcpyHostToDevice, L.stream));
+    HIP_TRY(hipMemcpyAsync(base + o_ids, ids, (size_t)n_total * 4, hipMemcpyHostToDevice, L.stream));
+    HIP_TRY(hipMemsetAsync(base + o_status, 0, (size_t)n_groups * 4, L.stream));
+    for (const Slice& s : slices) {
+        lcsgpu::GroupUpgmaArgs a{};
+        a.tri = (const uint16_t*)L.d_out.p;
+        a.sq = (float*)(base + o_sq);
+        a.jobs = (const lcsgpu::GroupUpgmaJob*)(base + o_jobs) + s.job0;
+        a.row0 = (const int64_t*)(base + o_row0) + s.row_at;
+        a.ids = (const int32_t*)(base + o_ids);
+        a.lens = (const uint32_t*)ctx->d_lens.p;
+        a.pow_f32 = (const float*)ctx->d_powf.p;
+        a.row_min = (float*)(base + o_min);
+        a.row_near = (int32_t*)(base + o_near);
+        a.left = (int32_t*)(base + o_left);
+        a.right = (int32_t*)(base + o_right);
+        a.status = (int32_t*)(base + o_status);
+        a.total_rows = s.rows;
+        a.n_jobs = (int32_t)s.n_jobs;
+        a.kind = distance_kind;
+        a.modified = modified ? 1 : 0;
+        a.max_m = s.max_m;
+        if (const hipError_t e = lcsgpu::launch_group_upgma(a, L.stream))
+            return fail(LCSGPU_E_HIP, "the batched UPGMA's launch failed: %s", hipGetErrorString(e));
+    }
+    if (!had_long) { // the call's kernel time: the triangles' launches and the slices' pairs
+        HIP_TRY(hipEventRecord(L.ev_stop, L.stream));
+        L.last_launches += 2 * (int)slices.size();
+    }
+    HIP_TRY(hipEventRecord(L.ev_done, L.stream));
+    HIP_TRY(hipEventSynchronize(L.ev_done));
+    if (hold.held) {
+        hold.g.unlock_shared();
+        hold.held = false;
+    }
+    // left | right | status are neighbours in the work buffer: one copy, then three
+    std::vector<char> back(o_min - o_left);
+    HIP_TRY(hipMemcpy(back.data(), base + o_left, back.size(), hipMemcpyDeviceToHost));
+    memcpy(out_left, back.data(), (size_t)n_nodes * 4);
+    memcpy(out_right, back.data() + (o_right - o_left), (size_t)n_nodes * 4);
+    memcpy(out_status, back.data() + (o_status - o_left), (size_t)n_groups * 4);
+    if (!had_long) finish_host_call(ctx, L);
+    else L.plan_in_flight = false;
+    return LCSGPU_OK;
+}
+
+int lcsgpu_upgma_batch(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* group_offsets, int32_t n_groups, int distance_kind,
+                       int modified, int32_t* out_left, int32_t* out_right, int32_t* out_status)
+{
+    try {
+        return upgma_batch_impl(ctx, ids, group_offsets, n_groups, distance_kind, modified, out_left, out_right, out_status);
+    } catch (const std::exception& e) { // no exception leaves the C-ABI
+        return fail(LCSGPU_E_NOMEM, "batched UPGMA: %s", e.what());
+    }
+}
+
 int lcsgpu_assign_seeds(lcsgpu_ctx* ctx, const int32_t* seed_ids, int32_t n_seeds, const int32_t* col_ids,
                         int32_t n_cols, int distance_kind, int32_t first_k, float* dist, int32_t* assign)
 {

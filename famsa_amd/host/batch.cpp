@@ -98,7 +98,8 @@ private:
 };
 
 // A file's slice of a chunk as the tree builders see it: ids 0 .. m - 1 = the file's sorted unique working order.  Prim's
-// edges come from the chunk's lcsgpu_mst_prim_batch, the triangle from its lcsgpu_lcs_triangles_batch; nothing is computed here.
+// edges come from the chunk's lcsgpu_mst_prim_batch, UPGMA's node records from its lcsgpu_upgma_batch, the triangle from its
+// lcsgpu_lcs_triangles_batch; nothing is computed here.
 class SliceLcsSource : public LcsSource {
 public:
     SliceLcsSource(const SeqSet& s, const std::vector<int>& in_of, bool sensitive) : s_(s), in_of_(in_of), sensitive_(sensitive) {}
@@ -106,6 +107,11 @@ public:
     const MstEdge* edges = nullptr;  // its m - 1 MST records, or NULL
     int edges_kind = -1;
     bool edges_triangle_orientation = false;
+    const int32_t* left = nullptr;   // its m - 1 UPGMA node records, or NULL
+    const int32_t* right = nullptr;
+    int nodes_kind = -1;
+    bool nodes_modified = false;
+    bool nodes_failed = false;       // the device found no finite nearest neighbour in this file
 
     int n() const override { return (int)in_of_.size(); }
     uint32_t length(int i) const override { return s_.length((size_t)in_of_[(size_t)i]); }
@@ -130,6 +136,16 @@ public:
         out.assign(edges, edges + (n() > 0 ? n() - 1 : 0));
         return true;
     }
+    bool upgma_nodes(int distance_kind, bool modified, std::vector<int32_t>& l, std::vector<int32_t>& r) override
+    {
+        if (!left || !right || distance_kind != nodes_kind || modified != nodes_modified) return false;
+        if (nodes_failed) // what the host builder says for such a file (trees.cpp)
+            throw std::runtime_error("UPGMA: no finite nearest neighbour (a pair with LCS 0?) -- the reference's "
+                                     "algorithm is undefined for this input");
+        l.assign(left, left + (n() > 0 ? n() - 1 : 0));
+        r.assign(right, right + (n() > 0 ? n() - 1 : 0));
+        return true;
+    }
 
 private:
     const SeqSet& s_;
@@ -146,6 +162,7 @@ struct Loaded {
 };
 
 bool is_mst(GT m) { return m == GT::MST_Prim || m == GT::SLINK; }
+bool is_upgma(GT m) { return m == GT::UPGMA || m == GT::UPGMA_modified; }
 
 } // namespace
 
@@ -159,7 +176,9 @@ int batch_group_max()
 {
     // The largest measured family size at which the chunks are ahead of both the one-file route on the same context and a
     // guide_tree loop, for -gt sl and for -gt upgma (profiles/batch_trees.txt: 849 / 316 files/s against 322 / 169 and 51 / 51
-    // at 1000 members; at 4000 -gt upgma gains nothing); never above LCSGPU_MST_BATCH_MAX_MEMBERS.
+    // at 1000 members; at 4000 -gt upgma gained nothing while its merges ran in the host builders -- with a workgroup per file
+    // it does, 59-63 against 24-28 files/s, profiles/batch_upgma.txt: the case for a limit per method, not taken yet); never
+    // above LCSGPU_MST_BATCH_MAX_MEMBERS.
     return std::max(0, std::min(4096, host_test_int("batch_group_max", 1000)));
 }
 
@@ -272,6 +291,7 @@ std::vector<BatchResult> guide_trees_newick_gpu(const std::vector<BatchJob>& job
     struct ChunkData {
         std::vector<LcsSource::MstEdge> edges[4]; // by (triangle orientation, distance kind)
         LcsBuf tri;
+        std::vector<int32_t> left[4], right[4], status[4]; // UPGMA by (modified, distance kind)
     };
     auto run_chunk = [&](const std::vector<size_t>& files) {
         GpuLcsSource* src = the_engine();
@@ -313,11 +333,14 @@ std::vector<BatchResult> guide_trees_newick_gpu(const std::vector<BatchJob>& job
 
             auto data = std::make_shared<ChunkData>();
             std::vector<char> sensitive(files.size(), 0);
-            std::vector<int> list_of(files.size(), -1);     // which of the five requests serves the file (4 = the triangles)
+            // which of the nine requests serves the file: 0 .. 3 = Prim's edges, 4 = the triangles, 5 .. 8 = UPGMA's node records
+            std::vector<int> list_of(files.size(), -1);
             std::vector<size_t> at(files.size(), 0);        // where its records / its triangle start in that request's result
-            std::vector<std::vector<int>> ids(5);
-            std::vector<std::vector<int64_t>> offs(5, std::vector<int64_t>{0});
-            std::vector<size_t> filled(5, 0);
+            std::vector<int> group_of(files.size(), 0);     // its list number inside the request
+            std::vector<std::vector<int>> ids(9);
+            std::vector<std::vector<int64_t>> offs(9, std::vector<int64_t>{0});
+            std::vector<size_t> filled(9, 0);
+            const bool upgma_on_host = host_test("batch_upgma_host");
             for (size_t k = 0; k < files.size(); ++k) {
                 const size_t i = files[k];
                 const Loaded& f = *loaded[i];
@@ -333,8 +356,11 @@ std::vector<BatchResult> guide_trees_newick_gpu(const std::vector<BatchJob>& job
                     continue;
                 }
                 if (is_mst(opt.method)) list = (opt.method == GT::SLINK ? 2 : 0) + (opt.dist == Distance::indel075_div_lcs ? 1 : 0);
+                else if (is_upgma(opt.method) && !upgma_on_host)
+                    list = 5 + (opt.method == GT::UPGMA_modified ? 2 : 0) + (opt.dist == Distance::indel075_div_lcs ? 1 : 0);
                 else list = 4;
                 list_of[k] = list;
+                group_of[k] = (int)offs[(size_t)list].size() - 1;
                 at[k] = filled[(size_t)list];
                 filled[(size_t)list] += list == 4 ? (size_t)m * (m - 1) / 2 : (size_t)(m - 1);
                 for (int a = 0; a < m; ++a) ids[(size_t)list].push_back(id0[k] + a);
@@ -345,6 +371,10 @@ std::vector<BatchResult> guide_trees_newick_gpu(const std::vector<BatchJob>& job
                     src->prim_edges_batch(ids[(size_t)list].data(), offs[(size_t)list].data(), (int)offs[(size_t)list].size() - 1, list & 1,
                                           list >= 2, data->edges[list]);
             if (offs[4].size() > 1) src->triangles_batch(ids[4].data(), offs[4].data(), (int)offs[4].size() - 1, data->tri);
+            for (int list = 5; list < 9; ++list)
+                if (offs[(size_t)list].size() > 1)
+                    src->upgma_nodes_batch(ids[(size_t)list].data(), offs[(size_t)list].data(), (int)offs[(size_t)list].size() - 1,
+                                           (list - 5) & 1, list >= 7, data->left[list - 5], data->right[list - 5], data->status[list - 5]);
             const double t2 = now_s();
             {
                 std::lock_guard<std::mutex> lk(tot_mu);
@@ -359,13 +389,20 @@ std::vector<BatchResult> guide_trees_newick_gpu(const std::vector<BatchJob>& job
                 const int list = list_of[k];
                 const size_t where = at[k];
                 const bool sens = sensitive[k] != 0;
-                pool.submit([&, i, list, where, sens, data] {
+                const int group = group_of[k];
+                pool.submit([&, i, list, where, group, sens, data] {
                     std::shared_ptr<Loaded> f = loaded[i];
                     try {
                         const double c0 = now_s();
                         SliceLcsSource view(f->s, f->in_of, sens);
                         if (list == 4) view.tri = data->tri.v16.data() + where;
-                        else if (list >= 0) {
+                        else if (list >= 5) {
+                            view.left = data->left[list - 5].data() + where;
+                            view.right = data->right[list - 5].data() + where;
+                            view.nodes_kind = (list - 5) & 1;
+                            view.nodes_modified = list >= 7;
+                            view.nodes_failed = data->status[list - 5][(size_t)group] != 0;
+                        } else if (list >= 0) {
                             view.edges = data->edges[list].data() + where;
                             view.edges_kind = list & 1;
                             view.edges_triangle_orientation = list >= 2;
@@ -378,6 +415,7 @@ std::vector<BatchResult> guide_trees_newick_gpu(const std::vector<BatchJob>& job
                             std::lock_guard<std::mutex> lk(tot_mu);
                             tot.newick_s += now_s() - c0;
                             ++tot.in_chunks;
+                            if (list >= 5) ++tot.device_upgma;
                         }
                         finish(i, std::move(r));
                     } catch (const std::exception& e) {

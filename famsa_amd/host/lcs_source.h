@@ -25,8 +25,9 @@ namespace famsa_host {
 // they were read instead of by length: measurements), leafmax=N (threads of that pool that may work on leaves while splits wait:
 // measurements), release_early / release_never / no_spare_tree / no_level_scratch (host memory of the tree heuristics as it was
 // before the second session of round 6: measurements), batch_pairs=N / batch_group_max=N (batch mode: the pair budget of a chunk and
-// the routing limit, batch.h -- tests force several chunks / the one-file route with them; unset, the defaults hold).  Not read on any
-// product default path beyond that.
+// the routing limit, batch.h -- tests force several chunks / the one-file route with them; unset, the defaults hold), batch_upgma_host
+// (batch mode: the merges of -gt upgma / upgma_modified files in the host builders over the chunk's triangles, as before
+// lcsgpu_upgma_batch: tests, measurements).  Not read on any product default path beyond that.
 bool host_test(const char* name);
 int host_test_int(const char* key, int dflt);
 // LCSGPU_PROFILE: stage / call statistics on stderr (the library prints its own under the same switch)
@@ -143,6 +144,11 @@ public:
     // ids[offsets[g] .. offsets[g + 1]), its max(m_g - 1, 0) records one list after the other, member numbers 0 .. m_g - 1
     void prim_edges_batch(const int* ids, const int64_t* offsets, int n_groups, int distance_kind, bool triangle_orientation,
                           std::vector<MstEdge>& edges);
+    // UPGMA of several id lists in one request (lcsgpu_upgma_batch on the first device): list g's max(m_g - 1, 0) node records
+    // one list after the other (leaves = member numbers 0 .. m_g - 1, internal node k = m_g + k); status[g] = 1: the list has
+    // no finite nearest neighbour and its records are unspecified
+    void upgma_nodes_batch(const int* ids, const int64_t* offsets, int n_groups, int distance_kind, bool modified,
+                           std::vector<int32_t>& left, std::vector<int32_t>& right, std::vector<int32_t>& status);
     // per uploaded sequence: 1 if it is orientation sensitive as a ref (lcsgpu_orientation_flags)
     const std::vector<uint8_t>& orientation_flags() const { return flags_; }
     bool upgma_nodes(int distance_kind, bool modified, std::vector<int32_t>& left, std::vector<int32_t>& right) override;

@@ -198,8 +198,8 @@ def guide_trees(fastas, gt="sl", distance="indel075_div_lcs", keep_duplicates=Fa
                 **medoid):
     """guide_tree for many files in ONE process on ONE engine context: a list with the Newick text (bytes) of every file, each
     what guide_tree gives for that file alone.  Families up to the routing limit are made together, chunk by chunk (one
-    workgroup per family for -gt sl / slink; the host builders over batched triangles for upgma / upgma_modified / nj); the
-    rest goes through the one-file path on the same context.  A file that fails does not stop the others: on_error="raise"
+    workgroup per family for -gt sl / slink and for upgma / upgma_modified; the host builder over batched triangles for
+    nj); the rest goes through the one-file path on the same context.  A file that fails does not stop the others: on_error="raise"
     raises the first failure after all files are done, on_error="return" puts the exception into that file's slot."""
     if on_error not in ("raise", "return"):
         raise ValueError("on_error must be 'raise' or 'return'")

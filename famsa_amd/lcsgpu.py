@@ -71,6 +71,7 @@ def load_library():
         "lcsgpu_multi_transport": (C.c_int, [vp, i32, C.c_char_p, sz]),
         "lcsgpu_upgma": (C.c_int, [vp, C.c_int, C.c_int, vp, vp]),
         "lcsgpu_nj": (C.c_int, [vp, C.c_int, vp, vp]),
+        "lcsgpu_upgma_batch": (C.c_int, [vp, pi32, C.POINTER(C.c_int64), i32, C.c_int, C.c_int, vp, vp, vp]),
         "lcsgpu_lcs_triangles_batch": (C.c_int, [vp, pi32, C.POINTER(C.c_int64), i32, vp, C.c_int]),
         "lcsgpu_assign_seeds": (C.c_int, [vp, pi32, i32, pi32, i32, C.c_int, i32, vp, vp]),
         "lcsgpu_clarans": (C.c_int, [vp, pi32, i32, C.c_int, i32, i32, C.c_float, i32, pi32]),
@@ -99,6 +100,7 @@ MST_EDGE = np.dtype([("from", np.int32), ("to", np.int32), ("dist", np.float64)]
 MST_KEY = np.dtype([("dist_bits", np.uint64), ("id", np.uint64)])                  # lcsgpu_mst_key
 MST_TRIANGLE_ORIENTATION = 0x100
 MST_BATCH_MAX_MEMBERS = 4096  # lcsgpu_mst_prim_batch: members of one group at most
+UPGMA_BATCH_MAX_MEMBERS = 4096  # lcsgpu_upgma_batch: members of one group at most
 MST_COMPUTE = 0x200  # lcsgpu_mst_shard_begin: the LCS launch itself does the local half (see include/lcsgpu.h)
 
 
@@ -326,6 +328,31 @@ class LcsGpu:
         right = np.zeros(max(self.n - 1, 1), dtype=np.int32)
         self._check(self._lib.lcsgpu_upgma(self._ctx, kind, int(modified), left.ctypes.data, right.ctypes.data))
         return left[: max(self.n - 1, 0)], right[: max(self.n - 1, 0)]
+
+    def upgma_batch(self, groups, kind=1, modified=False, out=None):
+        """UPGMA trees of several id lists of the uploaded set, one call (lcsgpu_upgma_batch): per list what upgma returns
+        for that list uploaded alone in list order (leaves = member numbers, internal node k = m + k).  Returns (a list of
+        (left, right) array pairs, the int32 status array: 0 = built, 1 = no finite nearest neighbour -- that list's
+        records are unspecified).  out (optional): the flat int32 arrays (left, right, status) the library writes into, sum
+        of max(m - 1, 0) records resp. len(groups) entries at least -- what is returned are then views of them."""
+        sizes = [len(g) for g in groups]
+        offs = np.zeros(len(groups) + 1, dtype=np.int64)
+        np.cumsum(sizes, out=offs[1:])
+        ids = np.ascontiguousarray(np.concatenate([np.asarray(g, np.int32) for g in groups])
+                                   if offs[-1] else np.zeros(0, np.int32), dtype=np.int32)
+        base = np.zeros(len(groups) + 1, dtype=np.int64)
+        np.cumsum([max(m - 1, 0) for m in sizes], out=base[1:])
+        if out is None:
+            out = (np.zeros(max(int(base[-1]), 1), np.int32), np.zeros(max(int(base[-1]), 1), np.int32),
+                   np.zeros(max(len(groups), 1), np.int32))
+        left, right, status = out
+        for arr, need in ((left, int(base[-1])), (right, int(base[-1])), (status, len(groups))):
+            assert arr.dtype == np.int32 and arr.flags.c_contiguous and len(arr) >= need
+        self._check(self._lib.lcsgpu_upgma_batch(self._ctx, ids.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                 offs.ctypes.data_as(C.POINTER(C.c_int64)), len(groups), int(kind),
+                                                 int(bool(modified)), left.ctypes.data, right.ctypes.data, status.ctypes.data))
+        return ([(left[base[g]:base[g + 1]], right[base[g]:base[g + 1]]) for g in range(len(groups))],
+                status[:len(groups)])
 
     def nj(self, kind=1):
         """Children (left, right) of internal nodes n..2n-2 of the neighbour-joining tree."""

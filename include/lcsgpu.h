@@ -376,6 +376,30 @@ int lcsgpu_lcs_triangles_batch(lcsgpu_ctx* ctx, const int32_t* ids, const int64_
 int lcsgpu_mst_prim_batch(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* group_offsets, int32_t n_groups,
                           int distance_kind, lcsgpu_mst_edge* out_edges);
 
+/* UPGMA of several id lists in one call (the guide trees of many small families): list g =
+ * ids[group_offsets[g] .. group_offsets[g+1]), m_g members, any ids of the uploaded set in any order.
+ * out_left / out_right (HOST) receive list g's max(m_g - 1, 0) node records at record offset
+ * sum_{h<g} max(m_h - 1, 0): exactly what lcsgpu_upgma returns for that list uploaded alone in list order --
+ * leaves are MEMBER numbers 0 .. m_g - 1, internal node k of the list is m_g + k.  modified != 0: the average
+ * 0.05f*(x+y)+0.9f*min(x,y) instead of (x+y)*0.5f.  The lists' triangles are computed as by
+ * lcsgpu_lcs_triangles_batch (ref = the LATER member of the list -- UPGMA::computeDistances's own orientation,
+ * so orientation-sensitive sequences are served like any other) and stay on the device; per slice of lists
+ * (at most LCSGPU_TUNE upgma_group_mb MB of float squares, 4096 by default, one list at least) one launch
+ * turns them into m_g x m_g float matrices (Transform<float, kind>: float pow table, IEEE float division,
+ * lcs == 0: FLT_MAX) with every row's first strict minimum, and one launch runs every list's m_g - 1 merges in
+ * a workgroup of its own, operation for operation as lcsgpu_upgma does.
+ * out_status (HOST, n_groups entries): 0 = the list's tree was built (also for lists of fewer than two
+ * members); 1 = no finite nearest neighbour (e.g. a sequence with LCS 0 to all others: the reference's
+ * algorithm is undefined there) -- that list's records are unspecified, the others are not affected and the
+ * call still returns LCSGPU_OK.
+ * LCSGPU_E_UNSUPPORTED (nothing computed, the outputs untouched): a list of more than
+ * LCSGPU_UPGMA_BATCH_MAX_MEMBERS members; a named sequence longer than 65535 residues -- lcsgpu_upgma on the
+ * list uploaded alone applies.  LCSGPU_E_NOMEM when the device cannot hold one slice.
+ * Replaces: UPGMA::computeDistances + UPGMA::computeTree (tree/UPGMA.cpp:75-109, 114-295), once per list. */
+#define LCSGPU_UPGMA_BATCH_MAX_MEMBERS 4096
+int lcsgpu_upgma_batch(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* group_offsets, int32_t n_groups,
+                       int distance_kind, int modified, int32_t* out_left, int32_t* out_right, int32_t* out_status);
+
 /* Seed assignment of one FastTree evaluation: for r = 0 .. n_seeds-1 in order,
  *   d = Transform<float>(LCS(ref = seed_ids[r], partner = col_ids[j]));  if (d < dist[j]) { dist[j] = d; assign[j] = first_k + r; }
  * dist / assign (HOST, n_cols entries each) are read and updated: the caller initialises them with the

@@ -8,7 +8,9 @@
   (c1) the same with FAMSA_HOST_TEST=batch_group_max=1: every file down the one-file route, but on the batch's ONE engine
        context -- what separates the routing (a workgroup per family against lcsgpu_mst_prim's rounds per file) from what
        the shared context and the parallel loading give on their own.  The routing limit is the largest size at which (c)
-       is not behind (c1).
+       is not behind (c1);
+  (ch) -gt upgma only: (c) with FAMSA_HOST_TEST=batch_upgma_host -- the chunks' triangles go to the host builders on the worker
+       threads, as before lcsgpu_upgma_batch ran a file's merges in a workgroup of its own.
 (a) and (b) cost a process start or an engine context per file, so they are timed on the first --files-a / --files-b files
 of a size (a rate does not need all 512); (c) takes all of them.  Medians of --reps timed runs after one warm-up.
 
@@ -17,6 +19,11 @@ of m members, lcsgpu_mst_prim on the group uploaded alone against lcsgpu_mst_pri
 the kernels' time (for the batch: its launches minus those of lcsgpu_lcs_triangles_batch on the same group = the Prim
 launch, with the square's expansion where that is on) -- with the packed triangle read as it is and with the expanded
 square.  (One group alone is the kernel's worst case: what it is for is many groups side by side, the `many` column.)
+And the same for lcsgpu_upgma_batch: wall time, kernels, the UPGMA launch pair alone (kernels minus those of
+lcsgpu_lcs_triangles_batch: the squares with the rows' initial keys, and the merges) and that per merge step.
+
+--gts / --skip-ab / --skip-mst-kernels / --cli narrow a run to some generators, to the batch legs, and to another build's
+famsa-gpu (a comparison with an earlier commit on the same machine).
 
 Writes everything to stdout and to --out (default profiles/batch_trees.txt)."""
 import argparse
@@ -102,6 +109,35 @@ def kernel_child(sizes, reps):
     eng.close()
 
 
+def upgma_child(sizes, reps):
+    """Runs in a child: one JSON line per group size for lcsgpu_upgma_batch."""
+    import famsa_amd
+    rng = np.random.Generator(np.random.PCG64(77))
+    eng = famsa_amd.LcsGpu(0)
+    for m in sizes:
+        seqs = family(rng, m)
+        eng.upload_seqs(seqs)
+        group = [np.arange(m, dtype=np.int32)]
+        many = max(1, min(64, 16384 // m))
+        groups = group * many
+        rec = {"m": m, "many": many}
+        for name, call in (("upgma", lambda: eng.upgma_batch(group, 1)), ("triangles", lambda: eng.lcs_triangles_batch(group)),
+                           ("many", lambda: eng.upgma_batch(groups, 1)), ("many_triangles", lambda: eng.lcs_triangles_batch(groups))):
+            res = call()
+            if name in ("upgma", "many"):
+                assert not res[1].any(), "a family without a tree"
+            wall, ms = [], []
+            for _ in range(reps):
+                t0 = time.perf_counter()
+                call()
+                wall.append(time.perf_counter() - t0)
+                ms.append(eng.last_kernel_ms()[0])
+            rec[name + "_wall_ms"] = 1e3 * statistics.median(wall)
+            rec[name + "_kernel_ms"] = statistics.median(ms)
+        print(json.dumps(rec), flush=True)
+    eng.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batch_trees.txt"))
@@ -111,11 +147,21 @@ def main():
     ap.add_argument("--scale", type=float, default=1.0, help="fraction of the 512 / 512 / 128 / 16 files to make")
     ap.add_argument("--kernel-sizes", default="50,200,256,500,1000,1500,2000,3000,4096")
     ap.add_argument("--skip-e2e", action="store_true")
+    ap.add_argument("--upgma-kernel-sizes", default="50,200,256,500,1000,2000,4096")
+    ap.add_argument("--gts", default="sl,upgma", help="the generators of the files-per-second table")
+    ap.add_argument("--skip-ab", action="store_true", help="no (a) / (b) legs: the batch legs only")
+    ap.add_argument("--skip-mst-kernels", action="store_true", help="no lcsgpu_mst_prim_batch kernel table")
+    ap.add_argument("--skip-upgma-kernels", action="store_true", help="no lcsgpu_upgma_batch kernel table (a build without the call)")
+    ap.add_argument("--cli", default=None, help="another build's famsa-gpu for the batch legs")
     ap.add_argument("--kernel-child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--upgma-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     ksizes = [int(x) for x in args.kernel_sizes.split(",") if x]
     if args.kernel_child:
         kernel_child(ksizes, args.reps)
+        return
+    if args.upgma_child:
+        upgma_child([int(x) for x in args.upgma_kernel_sizes.split(",") if x], args.reps)
         return
 
     lines = []
@@ -132,7 +178,7 @@ def main():
     say("## one group of m members in one process: lcsgpu_mst_prim (uploaded alone) against lcsgpu_mst_prim_batch")
     say("## wall = the call, kernels = its launches; prim = batch kernels - lcsgpu_lcs_triangles_batch kernels (the Prim launch")
     say("## and, with the square, its expansion); many = that many groups of m in one call, wall per group")
-    for square in (0, 1):
+    for square in (() if args.skip_mst_kernels else (0, 1)):
         say("# LCSGPU_TUNE=mst_batch_square=%d (%s)" % (square, "the expanded m x m square" if square else "the packed triangle as it is"))
         say("%6s %14s %14s %14s %14s %12s %16s" % ("m", "mst_prim wall", "mst_prim kern", "batch wall", "batch kern", "prim kern", "many: wall/group"))
         env = dict(os.environ)
@@ -148,11 +194,30 @@ def main():
                 r["m"], r["mst_prim_wall_ms"], r["mst_prim_kernel_ms"], r["batch_wall_ms"], r["batch_kernel_ms"],
                 r["batch_kernel_ms"] - r["triangles_kernel_ms"], r["many_wall_ms"] / r["many"], r["many"]))
         say()
+    if not args.skip_upgma_kernels:
+        say("## lcsgpu_upgma_batch: one group of m members, and many groups of m in one call (wall and kernels per group);")
+        say("## upgma = kernels - lcsgpu_lcs_triangles_batch kernels on the same groups (the squares + the merges); per step = upgma / (m - 1)")
+        say("%6s %12s %12s %12s %12s %18s %18s %14s" % ("m", "wall", "kernels", "upgma", "per step", "many: wall/group", "many: upgma/group", "many: per step"))
+        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--upgma-child", "--reps", str(args.reps), "--upgma-kernel-sizes",
+                            args.upgma_kernel_sizes], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        if p.returncode != 0:
+            say("FAILED: " + p.stderr[-1500:])
+            return 1
+        for l in p.stdout.splitlines():
+            r = json.loads(l)
+            one = r["upgma_kernel_ms"] - r["triangles_kernel_ms"]
+            many = (r["many_kernel_ms"] - r["many_triangles_kernel_ms"]) / r["many"]
+            say("%6d %9.3f ms %9.3f ms %9.3f ms %9.2f us %11.3f ms x%-3d %15.3f ms %11.2f us" % (
+                r["m"], r["upgma_wall_ms"], r["upgma_kernel_ms"], one, 1e3 * one / max(r["m"] - 1, 1), r["many_wall_ms"] / r["many"],
+                r["many"], many, 1e3 * many / max(r["m"] - 1, 1)))
+        say()
     if args.skip_e2e:
         return 0
 
     import famsa_amd
     from famsa_amd.hostlib import CLI
+    if args.cli:
+        CLI = args.cli
     rng = np.random.Generator(np.random.PCG64(2024))
     with tempfile.TemporaryDirectory() as tmp:
         files = {}
@@ -172,10 +237,11 @@ def main():
         say("## files per second; (a) one famsa-gpu process per file (first %d files), (b) famsa_amd.guide_tree in a loop in one" % args.files_a)
         say("## process (first %d files), (c) famsa-gpu -batch (all files of the size)" % args.files_b)
         say("## (c1) = (c) with every file sent down the one-file route on the batch's one engine context; (c4096) = (c) with the routing")
-        say("## limit at the kernel's cap: the chunks take every size")
-        say("%6s %6s %8s %12s %12s %12s %12s %14s %8s %8s" % ("gt", "m", "files", "(a) files/s", "(b) files/s", "(c) files/s", "(c1) files/s",
-                                                          "(c4096) files/s", "c / a", "c / b"))
-        for gt in ("sl", "upgma"):
+        say("## limit at the kernel's cap: the chunks take every size; (ch) = (c) with the UPGMA merges in the host builders")
+        say("%6s %6s %8s %12s %12s %12s %12s %14s %12s %8s %8s" % ("gt", "m", "files", "(a) files/s", "(b) files/s", "(c) files/s", "(c1) files/s",
+                                                               "(c4096) files/s", "(ch) files/s", "c / a", "c / b"))
+        nan = float("nan")
+        for gt in [g for g in args.gts.split(",") if g]:
             for m in SIZES:
                 fa, fb, fc = files[m][: args.files_a], files[m][: args.files_b], files[m]
 
@@ -200,20 +266,22 @@ def main():
                     subprocess.run([CLI, "-gt", gt, "-gt_export", "-batch", lst], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL,
                                    env=env)
 
-                a = len(fa) / median_of(run_a, args.reps)
-                b = len(fb) / median_of(run_b, args.reps)
+                a = nan if args.skip_ab else len(fa) / median_of(run_a, args.reps)
+                b = nan if args.skip_ab else len(fb) / median_of(run_b, args.reps)
                 c = len(fc) / median_of(run_c, args.reps)
                 c1 = len(fc) / median_of(lambda: run_c("batch_group_max=1"), args.reps)
                 c4096 = len(fc) / median_of(lambda: run_c("batch_group_max=4096"), args.reps)
-                say("%6s %6d %8d %12.1f %12.1f %12.1f %12.1f %14.1f %8.1f %8.1f" % (gt, m, len(fc), a, b, c, c1, c4096, c / a, c / b))
+                ch = len(fc) / median_of(lambda: run_c("batch_upgma_host"), args.reps) if gt.startswith("upgma") else nan
+                say("%6s %6d %8d %12.1f %12.1f %12.1f %12.1f %14.1f %12.1f %8.1f %8.1f" % (gt, m, len(fc), a, b, c, c1, c4096, ch, c / a, c / b))
                 # the batch's outputs are the one-file command's (spot check on the files (a) wrote last)
                 run_a()
                 one = [open(p, "rb").read() for p in outs(fa)]
                 run_c()
                 assert one == [open(p, "rb").read() for p in outs(fa)], (gt, m)
-        p = subprocess.run([CLI, "-gt", "sl", "-gt_export", "-batch", lst, "-v"], stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True)
+        last_gt = [g for g in args.gts.split(",") if g][-1]
+        p = subprocess.run([CLI, "-gt", last_gt, "-gt_export", "-batch", lst, "-v"], stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True)
         say()
-        say("## famsa-gpu -gt sl -gt_export -batch -v on the m = %d list" % SIZES[-1])
+        say("## famsa-gpu -gt %s -gt_export -batch -v on the m = %d list" % (last_gt, SIZES[-1]))
         for l in p.stderr.splitlines():
             say(l)
     return 0

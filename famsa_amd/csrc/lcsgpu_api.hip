@@ -54,41 +54,15 @@ struct Bucket {
     std::vector<RefItem> items;
 };
 
-// Which instantiation the refs of every half-word class run in.  A call's classes are launches one after the other on
-// one stream, and a launch that cannot fill the chip lasts as long as one of its workgroups however few it has: the
-// sample triangle of a FastTree split (2000 family members, four classes of ~500 refs, ~500 workgroups each) took four
-// times ~160 us (profiles/clarans_rounds_r04.txt: 4373 such launches, 1.22 s of kernel time for work that fills the chip
-// for 0.3 s).  So neighbouring classes are run together in the larger one's kernel -- a ref's half-words beyond its own
-// are all-ones no-ops (h_class) -- as long as the group stays below the workgroup count a launch is planned for
-// (refs_per_block_for: 2048).  wgs[h] = workgroups class h would have with the fewest refs per workgroup; classes that
-// fill the chip on their own (every large triangle) are left alone, as are the orientation-sensitive and long refs.
-void merge_small_classes(const double* wgs, int* target)
+RowsArgs rows_args_of_set(const lcsgpu_ctx* ctx)
 {
-    const double want = 2048.0;
-    for (int h = 0; h <= 64; ++h) target[h] = h;
-    int first = -1; // first class of the open group
-    double sum = 0;
-    auto close = [&](int last) {
-        if (first > 0)
-            for (int h = first; h <= last; ++h)
-                if (wgs[h] > 0) target[h] = last;
-        first = -1;
-        sum = 0;
-    };
-    int last_used = -1;
-    for (int h = 1; h <= 64; ++h) {
-        if (wgs[h] <= 0) continue;
-        if (first > 0 && sum + wgs[h] > want) close(last_used);
-        if (wgs[h] >= want) { // fills the chip by itself
-            close(last_used);
-            last_used = h;
-            continue;
-        }
-        if (first < 0) first = h;
-        sum += wgs[h];
-        last_used = h;
-    }
-    close(last_used);
+    RowsArgs a{};
+    a.tiles = (const uint8_t*)ctx->d_tiles.p;
+    a.tile_base = (const uint64_t*)ctx->d_tile_base.p;
+    a.lens = (const uint32_t*)ctx->d_lens.p;
+    a.masks = (const uint64_t*)ctx->d_masks.p;
+    a.mask_base = (const uint64_t*)ctx->d_mask_base.p;
+    return a;
 }
 
 // Split the refs by instantiated kernel (word-count class, quirk flag), keeping order.  col_blocks > 0: the
@@ -330,12 +304,7 @@ int run_rows(lcsgpu_ctx* ctx, Lane& L, int mode, const int32_t* ref_ids, int32_t
     for (size_t b = 0; b < buckets.size(); ++b) {
         const Bucket& bk = buckets[b];
         hipStream_t st = run_stream;
-        RowsArgs a{};
-        a.tiles = (const uint8_t*)ctx->d_tiles.p;
-        a.tile_base = (const uint64_t*)ctx->d_tile_base.p;
-        a.lens = (const uint32_t*)ctx->d_lens.p;
-        a.masks = (const uint64_t*)ctx->d_masks.p;
-        a.mask_base = (const uint64_t*)ctx->d_mask_base.p;
+        RowsArgs a = rows_args_of_set(ctx);
         a.n_refs = (int32_t)bk.items.size();
         if (is_contig[b]) {
             a.ref_ids = nullptr;

@@ -1,6 +1,7 @@
 // lcsgpu_fasttree.hip -- C-ABI entry points for the MedoidTree / PartTree recursion: the leaf matrices
 // of a split in one call, the seed assignment of an evaluation, CLARANS (kernels in
 // clarans_kernels.hip; here the host side: the two mt19937 streams and the batch of searches).
+// The job tables of the batched LCS launches are planned in job_plan.h; staged and launched here.
 #include "lcsgpu_internal.h"
 #include "fasttree_kernels.h"
 
@@ -9,6 +10,99 @@
 
 using namespace lcsgpu_impl;
 using lcsgpu::RowsArgs;
+
+static size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// no exception leaves the C-ABI (a std::bad_alloc of the host-side tables would end in std::terminate)
+template <class... Params, class... Args>
+static int guarded(const char* call, int (*impl)(Params...), Args... args)
+{
+    try {
+        return impl(args...);
+    } catch (const std::exception& e) {
+        return fail(LCSGPU_E_NOMEM, "%s: %s", call, e.what());
+    }
+}
+
+// where the tables of every bucket lie in a lane's plan buffers, behind the caller's own table at offset 0
+struct PlanLayout {
+    struct At { size_t id, end, c0, out, job; };
+    std::vector<At> at;
+    size_t bytes = 0;
+};
+
+// The buckets' tables, behind `head`, into L.h_plan; L.d_plan gets the room.  `reserved` (may be empty): called in between.
+static int stage_job_tables(Lane& L, const std::vector<JobBucket>& buckets, const void* head, size_t head_bytes, PlanLayout& lay,
+                            const std::function<void()>& reserved = nullptr)
+{
+    size_t bytes = 0;
+    auto take = [&](size_t n) { return std::exchange(bytes, bytes + ((n + 15) & ~(size_t)15)); }; // (16: enough for int64_t and int4)
+    take(head_bytes);
+    lay.at.clear();
+    for (const JobBucket& b : buckets) {
+        const size_t nr = b.refs.size();
+        lay.at.push_back(PlanLayout::At{take(nr * 4), take(nr * 8), take(nr * 4), take(nr * 8), take(b.jobs.size() * sizeof(Job))});
+    }
+    lay.bytes = bytes;
+    if (L.plan_in_flight) {
+        HIP_TRY(hipStreamSynchronize(L.stream));
+        L.plan_in_flight = false;
+    }
+    HIP_TRY(L.h_plan.reserve(L.h_plan.cap ? bytes : bytes * 3 / 2));
+    HIP_TRY(L.d_plan.reserve(L.d_plan.cap ? bytes : bytes * 3 / 2));
+    if (reserved) reserved();
+    char* h = (char*)L.h_plan.p;
+    memcpy(h, head, head_bytes);
+    for (size_t bi = 0; bi < buckets.size(); ++bi) {
+        const JobBucket& b = buckets[bi];
+        const PlanLayout::At& at = lay.at[bi];
+        for (size_t k = 0; k < b.refs.size(); ++k) {
+            ((int32_t*)(h + at.id))[k] = b.refs[k].id;
+            ((int64_t*)(h + at.end))[k] = b.refs[k].col_end;
+            ((int32_t*)(h + at.c0))[k] = b.refs[k].col0;
+            ((int64_t*)(h + at.out))[k] = b.refs[k].out0;
+        }
+        memcpy(h + at.job, b.jobs.data(), b.jobs.size() * sizeof(Job));
+    }
+    return LCSGPU_OK;
+}
+
+// The staged plan to the device and a launch per bucket into L.d_out, between L.ev_start and L.ev_stop.
+static int launch_job_tables(lcsgpu_ctx* ctx, Lane& L, const std::vector<JobBucket>& buckets, const PlanLayout& lay, int mode,
+                             const int32_t* d_col_ids, int64_t n_cols, int elem_size)
+{
+    static_assert(sizeof(Job) == sizeof(int4) && alignof(int4) <= 16, "RowsArgs::jobs");
+    RowsArgs a = rows_args_of_set(ctx);
+    a.col_ids = d_col_ids;
+    a.n_cols = (int32_t)n_cols;
+    a.out = L.d_out.p;
+    a.elem_size = elem_size;
+    a.mode = mode;
+    HIP_TRY(hipMemcpyAsync(L.d_plan.p, L.h_plan.p, lay.bytes, hipMemcpyHostToDevice, L.stream));
+    L.plan_in_flight = true;
+    L.last_launches = 0;
+    HIP_TRY(hipEventRecord(L.ev_start, L.stream));
+    const char* d = (const char*)L.d_plan.p;
+    for (size_t bi = 0; bi < buckets.size(); ++bi) {
+        const JobBucket& b = buckets[bi];
+        if (b.jobs.empty()) continue;
+        const PlanLayout::At& at = lay.at[bi];
+        a.n_refs = (int32_t)b.refs.size();
+        a.ref_ids = (const int32_t*)(d + at.id);
+        a.ref_rows = mode == lcsgpu::MODE_TRIANGLE ? (const int64_t*)(d + at.end) : nullptr;
+        a.ref_col0 = (const int32_t*)(d + at.c0);
+        a.ref_out0 = (const int64_t*)(d + at.out);
+        a.jobs = (const int4*)(d + at.job);
+        a.refs_per_block = b.refs_per_wg;
+        a.block_threads = b.narrow ? 64 : 0;
+        HIP_TRY(lcsgpu::launch_rows(b.bv, b.quirk, a, (int)b.jobs.size(), 1, L.stream));
+        trace_lcs_launch(b.bv, b.quirk, a, (long)b.jobs.size());
+        ++L.last_launches;
+    }
+    HIP_TRY(hipEventRecord(L.ev_stop, L.stream));
+    L.timing_valid = true;
+    return LCSGPU_OK;
+}
 
 // The packed LCS triangles of several id lists into lane L's result buffer (device memory), list g at pair offset
 // tri_base[g]: validation, planning and the launches of lcsgpu_lcs_triangles_batch.  *count = pairs in total (0: nothing to do).  On return the
@@ -81,151 +175,39 @@ static int batch_triangles_to_device(lcsgpu_ctx* ctx, Lane& L, const int32_t* id
         return LCSGPU_OK;
     }
 
-    // per instantiated kernel: its refs (in position order, so the refs of one list are adjacent) and its jobs
-    struct BatchBucket {
-        int bv;
-        bool quirk;
-        bool narrow; // one-wave workgroups, column blocks of 64: the refs of short lists (RowsArgs::block_threads)
-        std::vector<int32_t> ref_id, ref_col0;
-        std::vector<int64_t> ref_row, ref_out0;
-        std::vector<int32_t> ref_group;
-        std::vector<int4> jobs;
-        int refs_per_wg = 0;
-    };
-    std::vector<BatchBucket> buckets;
-    int index_of[320];
-    std::fill(index_of, index_of + 320, -1);
+    // the refs: every member but a list's first, which has no partner; rows and columns are positions in `ids`, a ref's
+    // columns end at its own row
     static const int narrow_max = tune_int("narrow_lists", 192); // lists up to that many members run in one-wave workgroups
-    int target[65];
-    {   // small neighbouring half-word classes share a launch (merge_small_classes, lcsgpu_api.hip)
-        double wgs[65] = {0}, inv_refs[65];
-        for (int h = 0; h <= 64; ++h) inv_refs[h] = 1.0 / lcsgpu::refs_per_block_for(h, false, 1, 1);
-        for (int32_t g = 0; g < n_groups; ++g)
-            for (int64_t p = group_offsets[g] + 1; p < group_offsets[g + 1]; ++p) {
-                if (cls[(size_t)p] & 0x80) continue;
-                const int h = cls[(size_t)p];
-                wgs[h] += (double)((p - group_offsets[g] + 255) / 256) * inv_refs[h];
-            }
-        merge_small_classes(wgs, target);
-    }
-    for (int32_t g = 0; g < n_groups; ++g)
-        for (int64_t p = group_offsets[g]; p < group_offsets[g + 1]; ++p) {
-            if (p == group_offsets[g]) continue; // the first member of a list has no partner
-            const int32_t id = ids[p];
-            const bool q = (cls[(size_t)p] & 0x80) != 0;
-            const int bv = q ? lcsgpu::quirk_h_class(ctx->lens[id]) : target[cls[(size_t)p]];
-            const bool narrow = !q && group_offsets[g + 1] - group_offsets[g] <= narrow_max;
-            const int key = bv * 2 + (q ? 1 : 0) + (narrow ? 160 : 0);
-            if (index_of[key] < 0) {
-                index_of[key] = (int)buckets.size();
-                buckets.push_back(BatchBucket{bv, q, narrow, {}, {}, {}, {}, {}, {}, 0});
-                BatchBucket& nb = buckets.back(); // (hundreds of lists: growing these step by step was a third of the planning time)
-                const size_t room = (size_t)n_total / (buckets.size() > 1 ? 4 : 1) + 16;
-                nb.ref_id.reserve(room);
-                nb.ref_row.reserve(room);
-                nb.ref_col0.reserve(room);
-                nb.ref_out0.reserve(room);
-                nb.ref_group.reserve(room);
-            }
-            BatchBucket& b = buckets[index_of[key]];
-            b.ref_id.push_back(id);
-            b.ref_row.push_back(p);
-            b.ref_col0.push_back((int32_t)group_offsets[g]);
-            b.ref_out0.push_back(tri_base[g]);
-            b.ref_group.push_back(g);
+    double inv_refs[65];
+    for (int h = 0; h <= 64; ++h) inv_refs[h] = 1.0 / lcsgpu::refs_per_block_for(h, false, 1, 1);
+    std::vector<JobRef> refs;
+    refs.reserve((size_t)n_total);
+    for (int32_t g = 0; g < n_groups; ++g) {
+        const int64_t g0 = group_offsets[g], g1 = group_offsets[g + 1];
+        for (int64_t p = g0 + 1; p < g1; ++p) {
+            const uint8_t c = cls[(size_t)p];
+            const bool q = (c & 0x80) != 0;
+            refs.push_back(JobRef{ids[p], g, (int32_t)g0, p, tri_base[g], q ? 0.0 : (double)((p - g0 + 255) / 256) * inv_refs[c], c,
+                                  (uint8_t)(q ? lcsgpu::quirk_h_class(ctx->lens[ids[p]]) : 0), !q && g1 - g0 <= narrow_max});
         }
-    size_t bytes = 0;
-    auto align16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    const size_t col_off = 0;
-    bytes += align16((size_t)n_total * 4);
-    std::vector<size_t> o_id(buckets.size()), o_row(buckets.size()), o_c0(buckets.size()), o_out(buckets.size()),
-        o_job(buckets.size());
-    for (size_t bi = 0; bi < buckets.size(); ++bi) {
-        BatchBucket& b = buckets[bi];
-        const int R = b.refs_per_wg = lcsgpu::refs_per_block_for(b.bv, b.quirk, (long)b.ref_id.size(), 1);
-        const size_t nr_all = b.ref_id.size();
-        b.jobs.reserve(nr_all / (size_t)std::max(1, R) * (b.narrow ? 3 : 5) + 16);
-        for (size_t k0 = 0; k0 < nr_all;) {
-            size_t k1 = k0 + 1;
-            while (k1 < nr_all && k1 - k0 < (size_t)R && b.ref_group[k1] == b.ref_group[k0]) ++k1;
-            const int32_t g0 = b.ref_col0[k0];
-            const int32_t max_row = (int32_t)b.ref_row[k1 - 1]; // rows ascend inside a list
-            for (int32_t c0 = g0; c0 < max_row; c0 += b.narrow ? 64 : 256)
-                b.jobs.push_back(make_int4((int)k0, (int)(k1 - k0), c0, max_row));
-            k0 = k1;
-        }
-        if (b.jobs.size() > 0x7fffffffu) return fail(LCSGPU_E_INVALID, "batch too large");
-        o_id[bi] = bytes; bytes += align16(nr_all * 4);
-        o_row[bi] = bytes; bytes += align16(nr_all * 8);
-        o_c0[bi] = bytes; bytes += align16(nr_all * 4);
-        o_out[bi] = bytes; bytes += align16(nr_all * 8);
-        o_job[bi] = bytes; bytes += align16(b.jobs.size() * sizeof(int4));
     }
+    std::vector<JobBucket> buckets;
+    if (!plan_jobs(refs, 1, lcsgpu::refs_per_block_for, buckets)) return fail(LCSGPU_E_INVALID, "batch too large");
     lap(1);
-    if (L.plan_in_flight) {
-        HIP_TRY(hipStreamSynchronize(L.stream));
-        L.plan_in_flight = false;
-    }
-    HIP_TRY(L.h_plan.reserve(L.h_plan.cap ? bytes : bytes * 3 / 2));
-    HIP_TRY(L.d_plan.reserve(L.d_plan.cap ? bytes : bytes * 3 / 2));
-    lap(2);
-    char* h = (char*)L.h_plan.p;
-    memcpy(h + col_off, ids, (size_t)n_total * 4);
-    for (size_t bi = 0; bi < buckets.size(); ++bi) {
-        const BatchBucket& b = buckets[bi];
-        memcpy(h + o_id[bi], b.ref_id.data(), b.ref_id.size() * 4);
-        memcpy(h + o_row[bi], b.ref_row.data(), b.ref_row.size() * 8);
-        memcpy(h + o_c0[bi], b.ref_col0.data(), b.ref_col0.size() * 4);
-        memcpy(h + o_out[bi], b.ref_out0.data(), b.ref_out0.size() * 8);
-        memcpy(h + o_job[bi], b.jobs.data(), b.jobs.size() * sizeof(int4));
-    }
+    PlanLayout lay;
+    int rc = stage_job_tables(L, buckets, ids, (size_t)n_total * 4, lay, [&] { lap(2); });
+    if (rc) return rc;
     lap(3);
     if (getenv("LCSGPU_PROFILE") && (++plan_calls % 20) == 0)
         fprintf(stderr, "triangle batches planned: %ld, thread-ms each: result buffer %.1f, lists + jobs %.1f, plan buffers %.1f, filling them %.1f (last: %lld ids, %d lists)\n",
                 plan_calls.load(), 1e-3 * plan_us[0] / plan_calls, 1e-3 * plan_us[1] / plan_calls, 1e-3 * plan_us[2] / plan_calls, 1e-3 * plan_us[3] / plan_calls,
                 (long long)n_total, n_groups);
     if (before_launch) before_launch();
-    HIP_TRY(hipMemcpyAsync(L.d_plan.p, h, bytes, hipMemcpyHostToDevice, L.stream));
-    L.plan_in_flight = true;
-    L.last_launches = 0;
-    const hipStream_t run_stream = L.stream;
-    HIP_TRY(hipEventRecord(L.ev_start, run_stream));
-    for (size_t bi = 0; bi < buckets.size(); ++bi) {
-        const BatchBucket& b = buckets[bi];
-        if (b.jobs.empty()) continue;
-        RowsArgs a{};
-        a.tiles = (const uint8_t*)ctx->d_tiles.p;
-        a.tile_base = (const uint64_t*)ctx->d_tile_base.p;
-        a.lens = (const uint32_t*)ctx->d_lens.p;
-        a.masks = (const uint64_t*)ctx->d_masks.p;
-        a.mask_base = (const uint64_t*)ctx->d_mask_base.p;
-        a.n_refs = (int32_t)b.ref_id.size();
-        char* d = (char*)L.d_plan.p;
-        a.ref_ids = (const int32_t*)(d + o_id[bi]);
-        a.ref_rows = (const int64_t*)(d + o_row[bi]);
-        a.ref_col0 = (const int32_t*)(d + o_c0[bi]);
-        a.ref_out0 = (const int64_t*)(d + o_out[bi]);
-        a.jobs = (const int4*)(d + o_job[bi]);
-        a.col_ids = (const int32_t*)(d + col_off);
-        a.n_cols = (int32_t)n_total;
-        a.out = L.d_out.p;
-        a.elem_size = elem_size;
-        a.mode = lcsgpu::MODE_TRIANGLE;
-        a.refs_per_block = b.refs_per_wg;
-        a.block_threads = b.narrow ? 64 : 0;
-        HIP_TRY(lcsgpu::launch_rows(b.bv, b.quirk, a, (int)b.jobs.size(), 1, run_stream));
-        trace_lcs_launch(b.bv, b.quirk, a, (long)b.jobs.size());
-        ++L.last_launches;
-    }
-    HIP_TRY(hipEventRecord(L.ev_stop, run_stream));
-    L.timing_valid = true;
-    return LCSGPU_OK;
+    return launch_job_tables(ctx, L, buckets, lay, lcsgpu::MODE_TRIANGLE, (const int32_t*)L.d_plan.p /* its first table */, n_total, elem_size);
 }
 
-extern "C" {
-
-int lcsgpu_lcs_triangles_batch(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* group_offsets, int32_t n_groups,
-                               void* out, int elem_size)
+static int lcs_triangles_batch_impl(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* group_offsets, int32_t n_groups, void* out,
+                                    int elem_size)
 {
     if (!ctx) return fail(LCSGPU_E_INVALID, "NULL ctx");
     // LCSGPU_PROFILE: where the calls' time goes, summed over the calling threads (printed by the 64th, 128th, ... call)
@@ -242,26 +224,19 @@ int lcsgpu_lcs_triangles_batch(lcsgpu_ctx* ctx, const int32_t* ids, const int64_
     std::vector<int64_t> tri_base;
     int64_t count = 0;
     bool had_long = false;
-    int rc;
-    {
-        struct Shared { // from the first launch until the kernels have run; the plan is made before, the results travel after
-            ComputeGate& g;
-            bool held = false;
-            ~Shared() { if (held) g.unlock_shared(); }
-        } hold{ctx->gate};
-        rc = batch_triangles_to_device(ctx, L, ids, group_offsets, n_groups, elem_size, tri_base, &count, &had_long, [&] {
-            lap(1);
-            hold.g.lock_shared();
-            hold.held = true;
-            lap(2);
-        });
-        if (rc || count <= 0) return rc;
-        if (!had_long) {
-            HIP_TRY(hipEventRecord(L.ev_done, L.stream));
-            HIP_TRY(hipEventSynchronize(L.ev_done));
-        }
-        lap(3);
+    GateHold hold{ctx->gate}; // from the first launch until the kernels have run
+    int rc = batch_triangles_to_device(ctx, L, ids, group_offsets, n_groups, elem_size, tri_base, &count, &had_long, [&] {
+        lap(1);
+        hold.lock();
+        lap(2);
+    });
+    if (rc || count <= 0) return rc;
+    if (!had_long) {
+        HIP_TRY(hipEventRecord(L.ev_done, L.stream));
+        HIP_TRY(hipEventSynchronize(L.ev_done));
     }
+    lap(3);
+    hold.release();
     if (!out) return fail(LCSGPU_E_INVALID, "NULL out");
     if (had_long) { // every list was synchronised already; the timing is in g_last
         HIP_TRY(hipMemcpy(out, L.d_out.p, (size_t)count * elem_size, hipMemcpyDeviceToHost));
@@ -279,6 +254,74 @@ int lcsgpu_lcs_triangles_batch(lcsgpu_ctx* ctx, const int32_t* ids, const int64_
     return LCSGPU_OK;
 }
 
+// What the per-group tree calls (lcsgpu_mst_prim_batch, lcsgpu_upgma_batch) check alike, in the order they always did.
+// per_group(g, members) and per_id(id) are the call's own refusals, asked where its limits stood: 0 = go on.
+template <class PerGroup, class PerId>
+static int check_groups(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* group_offsets, int32_t n_groups, int distance_kind,
+                        PerGroup&& per_group, PerId&& per_id)
+{
+    if (!ctx) return fail(LCSGPU_E_INVALID, "NULL ctx");
+    if (ctx->n < 0) return fail(LCSGPU_E_STATE, "no sequence set uploaded");
+    if (!valid_kind(distance_kind)) return fail(LCSGPU_E_INVALID, "unknown distance kind %d", distance_kind);
+    if (n_groups < 0 || (n_groups > 0 && !group_offsets)) return fail(LCSGPU_E_INVALID, "bad group table");
+    if (n_groups == 0) return LCSGPU_OK;
+    if (group_offsets[0] != 0) return fail(LCSGPU_E_INVALID, "group_offsets[0] must be 0");
+    const int64_t n_total = group_offsets[n_groups];
+    if (n_total < 0 || n_total > 0x7fffffff) return fail(LCSGPU_E_INVALID, "bad total id count");
+    if (n_total > 0 && !ids) return fail(LCSGPU_E_INVALID, "NULL ids");
+    for (int32_t g = 0; g < n_groups; ++g) {
+        const int64_t m = group_offsets[g + 1] - group_offsets[g];
+        if (m < 0) return fail(LCSGPU_E_INVALID, "group_offsets not ascending");
+        if (int rc = per_group(g, m)) return rc;
+    }
+    for (int64_t p = 0; p < n_total; ++p) {
+        if (ids[p] < 0 || ids[p] >= ctx->n) return fail(LCSGPU_E_INVALID, "id %d out of range", ids[p]);
+        if (int rc = per_id(ids[p])) return rc;
+    }
+    return LCSGPU_OK;
+}
+
+// The frame of a per-group tree call: a lane, the lists' 16-bit triangles in its result buffer, the compute gate from
+// the first launch until the group kernels have run.
+struct GroupCall {
+    lcsgpu_ctx* ctx;
+    LaneGuard guard;
+    Lane& L;
+    GateHold hold;
+    std::vector<int64_t> tri_base;
+    int64_t count = 0;
+    bool had_long = false;
+    explicit GroupCall(lcsgpu_ctx* c) : ctx(c), guard(c, LaneGuard::ANY), L(guard.lane()), hold{c->gate} {}
+    // the launches of lcsgpu_lcs_triangles_batch; then the jobs longest first (the groups that take the most steps start
+    // first), each with its triangle's place (Job::tri0 came in as the group)
+    template <class GroupJob>
+    int triangles(const int32_t* ids, const int64_t* group_offsets, int32_t n_groups, const char* what, std::vector<GroupJob>& jobs)
+    {
+        int rc = batch_triangles_to_device(ctx, L, ids, group_offsets, n_groups, 2, tri_base, &count, &had_long, [&] { hold.lock(); });
+        if (rc) return rc;
+        if (count <= 0) return fail(LCSGPU_E_STATE, "the batched %s found no pair to compute", what);
+        std::stable_sort(jobs.begin(), jobs.end(), [](const GroupJob& x, const GroupJob& y) { return x.m > y.m; });
+        for (GroupJob& job : jobs) job.tri0 = tri_base[(size_t)job.tri0];
+        return LCSGPU_OK;
+    }
+    // once the group kernels are queued (extra_launches of them, on top of the triangles'): the call's kernel time, the
+    // wait, the gate; then the caller's copy back and the accounting
+    int finish(int extra_launches, const std::function<int()>& copy_back)
+    {
+        if (!had_long) {
+            HIP_TRY(hipEventRecord(L.ev_stop, L.stream));
+            L.last_launches += extra_launches;
+        }
+        HIP_TRY(hipEventRecord(L.ev_done, L.stream));
+        HIP_TRY(hipEventSynchronize(L.ev_done));
+        hold.release();
+        if (int rc = copy_back()) return rc;
+        if (!had_long) finish_host_call(ctx, L);
+        else L.plan_in_flight = false;
+        return LCSGPU_OK;
+    }
+};
+
 // Prim's MST of many id lists: the lists' triangles by the launches of lcsgpu_lcs_triangles_batch, then ONE launch with a
 // workgroup per list (mst_kernels.hip, mst_group_prim_kernel), longest lists first.
 static int mst_prim_batch_impl(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* group_offsets, int32_t n_groups, int distance_kind,
@@ -286,40 +329,30 @@ static int mst_prim_batch_impl(lcsgpu_ctx* ctx, const int32_t* ids, const int64_
 {
     const bool triangle_orientation = (distance_kind & LCSGPU_MST_TRIANGLE_ORIENTATION) != 0;
     distance_kind &= ~LCSGPU_MST_TRIANGLE_ORIENTATION;
-    if (!ctx) return fail(LCSGPU_E_INVALID, "NULL ctx");
-    if (ctx->n < 0) return fail(LCSGPU_E_STATE, "no sequence set uploaded");
-    if (distance_kind != LCSGPU_DIST_INDEL_DIV_LCS && distance_kind != LCSGPU_DIST_INDEL075_DIV_LCS)
-        return fail(LCSGPU_E_INVALID, "unknown distance kind %d", distance_kind);
-    if (n_groups < 0 || (n_groups > 0 && !group_offsets)) return fail(LCSGPU_E_INVALID, "bad group table");
-    if (n_groups == 0) return LCSGPU_OK;
-    if (group_offsets[0] != 0) return fail(LCSGPU_E_INVALID, "group_offsets[0] must be 0");
-    const int64_t n_total = group_offsets[n_groups];
-    if (n_total < 0 || n_total > 0x7fffffff) return fail(LCSGPU_E_INVALID, "bad total id count");
-    if (n_total > 0 && !ids) return fail(LCSGPU_E_INVALID, "NULL ids");
     // everything that refuses comes first: nothing is computed, out_edges stays as it is
     std::vector<lcsgpu::GroupPrimJob> jobs;
     int64_t n_edges = 0, sq_elems = 0;
-    for (int32_t g = 0; g < n_groups; ++g) {
-        const int64_t m = group_offsets[g + 1] - group_offsets[g];
-        if (m < 0) return fail(LCSGPU_E_INVALID, "group_offsets not ascending");
-        if (m > LCSGPU_MST_BATCH_MAX_MEMBERS)
-            return fail(LCSGPU_E_UNSUPPORTED, "group %d has %lld members: the batched MST handles at most %d (use lcsgpu_mst_prim)", g,
-                        (long long)m, LCSGPU_MST_BATCH_MAX_MEMBERS);
-        if (m >= 2) {
-            jobs.push_back(lcsgpu::GroupPrimJob{(int64_t)g /* the group, until its triangle's place is known */, 0, n_edges, (int32_t)group_offsets[g], (int32_t)m});
-            n_edges += m - 1;
-        }
-    }
-    for (int64_t p = 0; p < n_total; ++p) {
-        const int32_t id = ids[p];
-        if (id < 0 || id >= ctx->n) return fail(LCSGPU_E_INVALID, "id %d out of range", id);
-        if (ctx->lens[(size_t)id] > 65535)
-            return fail(LCSGPU_E_UNSUPPORTED, "sequence %d is longer than 65535 residues: the batched MST keeps 16-bit LCS values", id);
-        if (!triangle_orientation && ctx->quirk[(size_t)id])
-            return fail(LCSGPU_E_UNSUPPORTED, "sequence %d is orientation sensitive: MSTPrim's distances depend on which endpoint is "
-                                              "the ref, the triangle does not hold them (use lcsgpu_mst_prim)", id);
-    }
-    if (jobs.empty()) return LCSGPU_OK;
+    int rc = check_groups(
+        ctx, ids, group_offsets, n_groups, distance_kind,
+        [&](int32_t g, int64_t m) {
+            if (m > LCSGPU_MST_BATCH_MAX_MEMBERS)
+                return fail(LCSGPU_E_UNSUPPORTED, "group %d has %lld members: the batched MST handles at most %d (use lcsgpu_mst_prim)", g,
+                            (long long)m, LCSGPU_MST_BATCH_MAX_MEMBERS);
+            if (m >= 2) {
+                jobs.push_back(lcsgpu::GroupPrimJob{(int64_t)g /* the group, until its triangle's place is known */, 0, n_edges, (int32_t)group_offsets[g], (int32_t)m});
+                n_edges += m - 1;
+            }
+            return 0;
+        },
+        [&](int32_t id) {
+            if (ctx->lens[(size_t)id] > 65535)
+                return fail(LCSGPU_E_UNSUPPORTED, "sequence %d is longer than 65535 residues: the batched MST keeps 16-bit LCS values", id);
+            if (!triangle_orientation && ctx->quirk[(size_t)id])
+                return fail(LCSGPU_E_UNSUPPORTED, "sequence %d is orientation sensitive: MSTPrim's distances depend on which endpoint is "
+                                                  "the ref, the triangle does not hold them (use lcsgpu_mst_prim)", id);
+            return 0;
+        });
+    if (rc || jobs.empty()) return rc;
     if (!out_edges) return fail(LCSGPU_E_INVALID, "NULL out_edges");
     // The LCS values of (cur, v) from the group's expanded m x m square (one contiguous row per step) or -- LCSGPU_TUNE
     // mst_batch_square=0 -- from the packed triangle as it is (v > cur: a strided 2-byte gather).  A step is latency more
@@ -328,35 +361,20 @@ static int mst_prim_batch_impl(lcsgpu_ctx* ctx, const int32_t* ids, const int64_
     // for twice the triangles' memory again.
     static const int use_square = tune_int("mst_batch_square", 1);
 
-    LaneGuard guard(ctx, LaneGuard::ANY);
-    Lane& L = guard.lane();
-    std::vector<int64_t> tri_base;
-    int64_t count = 0;
-    bool had_long = false;
-    struct Shared { // from the first launch until the kernels have run (lcsgpu_lcs_triangles_batch)
-        ComputeGate& g;
-        bool held = false;
-        ~Shared() { if (held) g.unlock_shared(); }
-    } hold{ctx->gate};
-    int rc = batch_triangles_to_device(ctx, L, ids, group_offsets, n_groups, 2, tri_base, &count, &had_long, [&] {
-        hold.g.lock_shared();
-        hold.held = true;
-    });
+    GroupCall call(ctx);
+    Lane& L = call.L;
+    rc = call.triangles(ids, group_offsets, n_groups, "MST", jobs);
     if (rc) return rc;
-    if (count <= 0) return fail(LCSGPU_E_STATE, "the batched MST found no pair to compute");
-    // longest first: the groups that take the most steps start first
-    std::stable_sort(jobs.begin(), jobs.end(), [](const lcsgpu::GroupPrimJob& x, const lcsgpu::GroupPrimJob& y) { return x.m > y.m; });
+    const int64_t n_total = group_offsets[n_groups];
     std::vector<int64_t> row0(jobs.size() + 1, 0);
     int32_t max_m = 0;
     for (size_t j = 0; j < jobs.size(); ++j) {
         lcsgpu::GroupPrimJob& job = jobs[j];
-        job.tri0 = tri_base[(size_t)job.tri0];
         job.sq0 = sq_elems;
         sq_elems += (int64_t)job.m * job.m;
         row0[j + 1] = row0[j] + job.m;
         max_m = std::max(max_m, job.m);
     }
-    auto a256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t o_jobs = 0, o_row0 = o_jobs + a256(jobs.size() * sizeof(lcsgpu::GroupPrimJob)), o_ids = o_row0 + a256(row0.size() * 8),
                  o_edges = o_ids + a256((size_t)n_total * 4), o_sq = o_edges + a256((size_t)n_edges * sizeof(lcsgpu_mst_edge)),
                  total = o_sq + (use_square ? a256((size_t)sq_elems * 2) : 0);
@@ -382,31 +400,11 @@ static int mst_prim_batch_impl(lcsgpu_ctx* ctx, const int32_t* ids, const int64_
     a.max_m = max_m;
     if (const hipError_t e = lcsgpu::launch_group_prim(a, L.stream))
         return fail(LCSGPU_E_HIP, "the batched MST's launch failed: %s", hipGetErrorString(e));
-    if (!had_long) { // the call's kernel time: the triangles' launches and this one
-        HIP_TRY(hipEventRecord(L.ev_stop, L.stream));
-        L.last_launches += use_square ? 2 : 1;
-    }
-    HIP_TRY(hipEventRecord(L.ev_done, L.stream));
-    HIP_TRY(hipEventSynchronize(L.ev_done));
-    if (hold.held) {
-        hold.g.unlock_shared();
-        hold.held = false;
-    }
     static_assert(sizeof(lcsgpu_mst_edge) == sizeof(lcsgpu::MstEdge), "edge records");
-    HIP_TRY(hipMemcpy(out_edges, base + o_edges, (size_t)n_edges * sizeof(lcsgpu_mst_edge), hipMemcpyDeviceToHost));
-    if (!had_long) finish_host_call(ctx, L);
-    else L.plan_in_flight = false;
-    return LCSGPU_OK;
-}
-
-int lcsgpu_mst_prim_batch(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* group_offsets, int32_t n_groups, int distance_kind,
-                          lcsgpu_mst_edge* out_edges)
-{
-    try {
-        return mst_prim_batch_impl(ctx, ids, group_offsets, n_groups, distance_kind, out_edges);
-    } catch (const std::exception& e) { // no exception leaves the C-ABI
-        return fail(LCSGPU_E_NOMEM, "batched MST: %s", e.what());
-    }
+    return call.finish(use_square ? 2 : 1, [&] {
+        HIP_TRY(hipMemcpy(out_edges, base + o_edges, (size_t)n_edges * sizeof(lcsgpu_mst_edge), hipMemcpyDeviceToHost));
+        return LCSGPU_OK;
+    });
 }
 
 // UPGMA of many id lists: the lists' triangles by the launches of lcsgpu_lcs_triangles_batch, then per slice of lists a
@@ -415,39 +413,30 @@ int lcsgpu_mst_prim_batch(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* gr
 static int upgma_batch_impl(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* group_offsets, int32_t n_groups, int distance_kind,
                             int modified, int32_t* out_left, int32_t* out_right, int32_t* out_status)
 {
-    if (!ctx) return fail(LCSGPU_E_INVALID, "NULL ctx");
-    if (ctx->n < 0) return fail(LCSGPU_E_STATE, "no sequence set uploaded");
-    if (distance_kind != LCSGPU_DIST_INDEL_DIV_LCS && distance_kind != LCSGPU_DIST_INDEL075_DIV_LCS)
-        return fail(LCSGPU_E_INVALID, "unknown distance kind %d", distance_kind);
-    if (n_groups < 0 || (n_groups > 0 && !group_offsets)) return fail(LCSGPU_E_INVALID, "bad group table");
-    if (n_groups == 0) return LCSGPU_OK;
-    if (group_offsets[0] != 0) return fail(LCSGPU_E_INVALID, "group_offsets[0] must be 0");
-    const int64_t n_total = group_offsets[n_groups];
-    if (n_total < 0 || n_total > 0x7fffffff) return fail(LCSGPU_E_INVALID, "bad total id count");
-    if (n_total > 0 && !ids) return fail(LCSGPU_E_INVALID, "NULL ids");
     // everything that refuses comes first: nothing is computed, the outputs stay as they are
     std::vector<lcsgpu::GroupUpgmaJob> jobs;
     int64_t n_nodes = 0;
-    for (int32_t g = 0; g < n_groups; ++g) {
-        const int64_t m = group_offsets[g + 1] - group_offsets[g];
-        if (m < 0) return fail(LCSGPU_E_INVALID, "group_offsets not ascending");
-        if (m > LCSGPU_UPGMA_BATCH_MAX_MEMBERS)
-            return fail(LCSGPU_E_UNSUPPORTED, "group %d has %lld members: the batched UPGMA handles at most %d (use lcsgpu_upgma)", g,
-                        (long long)m, LCSGPU_UPGMA_BATCH_MAX_MEMBERS);
-        if (m >= 2) {
-            jobs.push_back(lcsgpu::GroupUpgmaJob{(int64_t)g /* the group, until its triangle's place is known */, 0, n_nodes,
-                                                 (int32_t)group_offsets[g], (int32_t)m, g, 0});
-            n_nodes += m - 1;
-        }
-    }
-    for (int64_t p = 0; p < n_total; ++p) {
-        const int32_t id = ids[p];
-        if (id < 0 || id >= ctx->n) return fail(LCSGPU_E_INVALID, "id %d out of range", id);
-        if (ctx->lens[(size_t)id] > 65535)
-            return fail(LCSGPU_E_UNSUPPORTED, "sequence %d is longer than 65535 residues: the batched UPGMA keeps 16-bit LCS values", id);
-        // (orientation-sensitive members are served: the triangle's orientation, ref = the later member, IS
-        // UPGMA::computeDistances's)
-    }
+    int rc = check_groups(
+        ctx, ids, group_offsets, n_groups, distance_kind,
+        [&](int32_t g, int64_t m) {
+            if (m > LCSGPU_UPGMA_BATCH_MAX_MEMBERS)
+                return fail(LCSGPU_E_UNSUPPORTED, "group %d has %lld members: the batched UPGMA handles at most %d (use lcsgpu_upgma)", g,
+                            (long long)m, LCSGPU_UPGMA_BATCH_MAX_MEMBERS);
+            if (m >= 2) {
+                jobs.push_back(lcsgpu::GroupUpgmaJob{(int64_t)g /* the group, until its triangle's place is known */, 0, n_nodes,
+                                                     (int32_t)group_offsets[g], (int32_t)m, g, 0});
+                n_nodes += m - 1;
+            }
+            return 0;
+        },
+        [&](int32_t id) {
+            // (orientation-sensitive members are served: the triangle's orientation, ref = the later member, IS
+            // UPGMA::computeDistances's)
+            if (ctx->lens[(size_t)id] > 65535)
+                return fail(LCSGPU_E_UNSUPPORTED, "sequence %d is longer than 65535 residues: the batched UPGMA keeps 16-bit LCS values", id);
+            return 0;
+        });
+    if (rc || n_groups == 0) return rc;
     if (!out_status) return fail(LCSGPU_E_INVALID, "NULL out_status");
     if (n_nodes > 0 && (!out_left || !out_right)) return fail(LCSGPU_E_INVALID, "NULL out_left / out_right");
     if (jobs.empty()) {
@@ -457,24 +446,11 @@ static int upgma_batch_impl(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* 
     // the float squares of a launch pair: at most this many MB (a slice always holds at least one group)
     static const int slice_mb = std::max(1, tune_int("upgma_group_mb", 4096));
 
-    LaneGuard guard(ctx, LaneGuard::ANY);
-    Lane& L = guard.lane();
-    std::vector<int64_t> tri_base;
-    int64_t count = 0;
-    bool had_long = false;
-    struct Shared { // from the first launch until the kernels have run (lcsgpu_lcs_triangles_batch)
-        ComputeGate& g;
-        bool held = false;
-        ~Shared() { if (held) g.unlock_shared(); }
-    } hold{ctx->gate};
-    int rc = batch_triangles_to_device(ctx, L, ids, group_offsets, n_groups, 2, tri_base, &count, &had_long, [&] {
-        hold.g.lock_shared();
-        hold.held = true;
-    });
+    GroupCall call(ctx);
+    Lane& L = call.L;
+    rc = call.triangles(ids, group_offsets, n_groups, "UPGMA", jobs);
     if (rc) return rc;
-    if (count <= 0) return fail(LCSGPU_E_STATE, "the batched UPGMA found no pair to compute");
-    // longest first: the groups that take the most steps start first
-    std::stable_sort(jobs.begin(), jobs.end(), [](const lcsgpu::GroupUpgmaJob& x, const lcsgpu::GroupUpgmaJob& y) { return x.m > y.m; });
+    const int64_t n_total = group_offsets[n_groups];
     struct Slice { size_t job0, n_jobs, row_at; int64_t rows, sq_elems; int32_t max_m; };
     std::vector<Slice> slices;
     std::vector<int64_t> row0; // per slice: the prefix sums of m over its jobs, one slice after the other
@@ -482,7 +458,6 @@ static int upgma_batch_impl(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* 
     int64_t max_sq = 0, max_rows = 0;
     for (size_t j = 0; j < jobs.size(); ++j) {
         lcsgpu::GroupUpgmaJob& job = jobs[j];
-        job.tri0 = tri_base[(size_t)job.tri0];
         const int64_t sq = (int64_t)job.m * job.m;
         if (slices.empty() || slices.back().sq_elems + sq > slice_elems) {
             slices.push_back(Slice{j, 0, row0.size(), 0, 0, job.m});
@@ -497,7 +472,6 @@ static int upgma_batch_impl(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* 
         max_sq = std::max(max_sq, s.sq_elems);
         max_rows = std::max(max_rows, s.rows);
     }
-    auto a256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t o_jobs = 0, o_row0 = o_jobs + a256(jobs.size() * sizeof(lcsgpu::GroupUpgmaJob)), o_ids = o_row0 + a256(row0.size() * 8),
                  o_left = o_ids + a256((size_t)n_total * 4), o_right = o_left + a256((size_t)n_nodes * 4),
                  o_status = o_right + a256((size_t)n_nodes * 4), o_min = o_status + a256((size_t)n_groups * 4),
@@ -532,44 +506,22 @@ static int upgma_batch_impl(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* 
         if (const hipError_t e = lcsgpu::launch_group_upgma(a, L.stream))
             return fail(LCSGPU_E_HIP, "the batched UPGMA's launch failed: %s", hipGetErrorString(e));
     }
-    if (!had_long) { // the call's kernel time: the triangles' launches and the slices' pairs
-        HIP_TRY(hipEventRecord(L.ev_stop, L.stream));
-        L.last_launches += 2 * (int)slices.size();
-    }
-    HIP_TRY(hipEventRecord(L.ev_done, L.stream));
-    HIP_TRY(hipEventSynchronize(L.ev_done));
-    if (hold.held) {
-        hold.g.unlock_shared();
-        hold.held = false;
-    }
-    // left | right | status are neighbours in the work buffer: one copy, then three
-    std::vector<char> back(o_min - o_left);
-    HIP_TRY(hipMemcpy(back.data(), base + o_left, back.size(), hipMemcpyDeviceToHost));
-    memcpy(out_left, back.data(), (size_t)n_nodes * 4);
-    memcpy(out_right, back.data() + (o_right - o_left), (size_t)n_nodes * 4);
-    memcpy(out_status, back.data() + (o_status - o_left), (size_t)n_groups * 4);
-    if (!had_long) finish_host_call(ctx, L);
-    else L.plan_in_flight = false;
-    return LCSGPU_OK;
+    return call.finish(2 * (int)slices.size(), [&] { // left | right | status are neighbours in the work buffer: one copy, then three
+        std::vector<char> back(o_min - o_left);
+        HIP_TRY(hipMemcpy(back.data(), base + o_left, back.size(), hipMemcpyDeviceToHost));
+        memcpy(out_left, back.data(), (size_t)n_nodes * 4);
+        memcpy(out_right, back.data() + (o_right - o_left), (size_t)n_nodes * 4);
+        memcpy(out_status, back.data() + (o_status - o_left), (size_t)n_groups * 4);
+        return LCSGPU_OK;
+    });
 }
 
-int lcsgpu_upgma_batch(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* group_offsets, int32_t n_groups, int distance_kind,
-                       int modified, int32_t* out_left, int32_t* out_right, int32_t* out_status)
-{
-    try {
-        return upgma_batch_impl(ctx, ids, group_offsets, n_groups, distance_kind, modified, out_left, out_right, out_status);
-    } catch (const std::exception& e) { // no exception leaves the C-ABI
-        return fail(LCSGPU_E_NOMEM, "batched UPGMA: %s", e.what());
-    }
-}
-
-int lcsgpu_assign_seeds(lcsgpu_ctx* ctx, const int32_t* seed_ids, int32_t n_seeds, const int32_t* col_ids,
-                        int32_t n_cols, int distance_kind, int32_t first_k, float* dist, int32_t* assign)
+static int assign_seeds_impl(lcsgpu_ctx* ctx, const int32_t* seed_ids, int32_t n_seeds, const int32_t* col_ids, int32_t n_cols,
+                             int distance_kind, int32_t first_k, float* dist, int32_t* assign)
 {
     if (!ctx) return fail(LCSGPU_E_INVALID, "NULL ctx");
     if (ctx->n < 0) return fail(LCSGPU_E_STATE, "no sequence set uploaded");
-    if (distance_kind != LCSGPU_DIST_INDEL_DIV_LCS && distance_kind != LCSGPU_DIST_INDEL075_DIV_LCS)
-        return fail(LCSGPU_E_INVALID, "unknown distance kind %d", distance_kind);
+    if (!valid_kind(distance_kind)) return fail(LCSGPU_E_INVALID, "unknown distance kind %d", distance_kind);
     if (n_seeds < 0 || n_cols < 0) return fail(LCSGPU_E_INVALID, "negative count");
     if (n_seeds == 0 || n_cols == 0) return LCSGPU_OK;
     if (!seed_ids || !col_ids || !dist || !assign) return fail(LCSGPU_E_INVALID, "NULL argument");
@@ -581,7 +533,6 @@ int lcsgpu_assign_seeds(lcsgpu_ctx* ctx, const int32_t* seed_ids, int32_t n_seed
     const int elem = ctx->max_len > 65535 ? 4 : 2;
     // column chunks: the LCS rectangle of a chunk stays below 256 MB
     const int32_t chunk = (int32_t)std::max<int64_t>(4096, std::min<int64_t>(n_cols, ((int64_t)256 << 20) / ((int64_t)n_seeds * elem)));
-    auto a256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t o_seeds = 0, o_cols = o_seeds + a256((size_t)n_seeds * 4), o_dist = o_cols + a256((size_t)chunk * 4),
                  o_assign = o_dist + a256((size_t)chunk * 4), total = o_assign + a256((size_t)chunk * 4);
     HIP_TRY(L.d_work.reserve(total));
@@ -614,13 +565,12 @@ int lcsgpu_assign_seeds(lcsgpu_ctx* ctx, const int32_t* seed_ids, int32_t n_seed
     return LCSGPU_OK;
 }
 
-int lcsgpu_assign_seeds_batch(lcsgpu_ctx* ctx, const int32_t* seed_ids, const int64_t* seed_offsets, const int32_t* col_ids,
-                              const int64_t* col_offsets, int32_t n_jobs, int distance_kind, float* dist, int32_t* assign)
+static int assign_seeds_batch_impl(lcsgpu_ctx* ctx, const int32_t* seed_ids, const int64_t* seed_offsets, const int32_t* col_ids,
+                                   const int64_t* col_offsets, int32_t n_jobs, int distance_kind, float* dist, int32_t* assign)
 {
     if (!ctx) return fail(LCSGPU_E_INVALID, "NULL ctx");
     if (ctx->n < 0) return fail(LCSGPU_E_STATE, "no sequence set uploaded");
-    if (distance_kind != LCSGPU_DIST_INDEL_DIV_LCS && distance_kind != LCSGPU_DIST_INDEL075_DIV_LCS)
-        return fail(LCSGPU_E_INVALID, "unknown distance kind %d", distance_kind);
+    if (!valid_kind(distance_kind)) return fail(LCSGPU_E_INVALID, "unknown distance kind %d", distance_kind);
     if (n_jobs < 0 || (n_jobs > 0 && (!seed_offsets || !col_offsets))) return fail(LCSGPU_E_INVALID, "bad job tables");
     if (n_jobs == 0) return LCSGPU_OK;
     if (seed_offsets[0] != 0 || col_offsets[0] != 0) return fail(LCSGPU_E_INVALID, "offsets must start at 0");
@@ -646,8 +596,8 @@ int lcsgpu_assign_seeds_batch(lcsgpu_ctx* ctx, const int32_t* seed_ids, const in
                 dist[c0 + c] = std::numeric_limits<float>::infinity();
                 assign[c0 + c] = 0;
             }
-            int rc = lcsgpu_assign_seeds(ctx, seed_ids + seed_offsets[j], (int32_t)(seed_offsets[j + 1] - seed_offsets[j]), col_ids + c0, (int32_t)nc,
-                                         distance_kind, 0, dist + c0, assign + c0);
+            int rc = assign_seeds_impl(ctx, seed_ids + seed_offsets[j], (int32_t)(seed_offsets[j + 1] - seed_offsets[j]), col_ids + c0, (int32_t)nc,
+                                       distance_kind, 0, dist + c0, assign + c0);
             if (rc) return rc;
         }
         return LCSGPU_OK;
@@ -675,7 +625,8 @@ int lcsgpu_assign_seeds_batch(lcsgpu_ctx* ctx, const int32_t* seed_ids, const in
     HIP_TRY(hipMemcpyAsync(L.d_draws.p, seed_ids, (size_t)n_seeds_all * 4, hipMemcpyHostToDevice, L.stream));
     double ms = 0;
     int launches = 0;
-    auto a256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    std::vector<JobRef> refs;
+    std::vector<JobBucket> buckets;
     for (size_t p0 = 0; p0 < pieces.size();) {
         // the launch: pieces [p0, p1) as far as their columns are contiguous and the rectangles fit
         size_t p1 = p0;
@@ -691,32 +642,9 @@ int lcsgpu_assign_seeds_batch(lcsgpu_ctx* ctx, const int32_t* seed_ids, const in
         const int64_t C0 = pieces[p0].c0, C1 = pieces[p1 - 1].c1, nc = C1 - C0;
         if (nc > 0x7fffff00) return fail(LCSGPU_E_INVALID, "a job's column range is too long for one launch");
         const int32_t np = (int32_t)(p1 - p0);
-        // per instantiated kernel: its refs and jobs
-        struct Bucket {
-            int bv;
-            bool quirk;
-            std::vector<int32_t> ref_id, ref_col0, ref_piece;
-            std::vector<int64_t> ref_out0;
-            std::vector<int4> jobs;
-            int refs_per_wg = 0;
-        };
-        std::vector<Bucket> buckets;
-        int index_of[160];
-        std::fill(index_of, index_of + 160, -1);
+        // the refs: every seed of every piece, a row of the piece's rectangle each; columns are relative to the launch's first
         std::vector<lcsgpu::AssignPiece> table((size_t)np);
-        int target[65];
-        {
-            double wgs[65] = {0};
-            for (size_t p = p0; p < p1; ++p) {
-                const Piece& pc = pieces[p];
-                for (int64_t s = seed_offsets[pc.job]; s < seed_offsets[pc.job + 1]; ++s) {
-                    if (ctx->quirk[seed_ids[s]]) continue;
-                    const int h = lcsgpu::h_class(ctx->lens[seed_ids[s]]);
-                    wgs[h] += (double)((pc.c1 - pc.c0 + 255) / 256) / lcsgpu::refs_per_block_for(h, false, 1, 1);
-                }
-            }
-            merge_small_classes(wgs, target);
-        }
+        refs.clear();
         int64_t out_at = 0;
         for (size_t p = p0; p < p1; ++p) {
             const Piece& pc = pieces[p];
@@ -724,96 +652,29 @@ int lcsgpu_assign_seeds_batch(lcsgpu_ctx* ctx, const int32_t* seed_ids, const in
             table[p - p0] = lcsgpu::AssignPiece{out_at, (int32_t)(pc.c0 - C0), (int32_t)w, (int32_t)s0, (int32_t)ns};
             for (int64_t r = 0; r < ns; ++r) {
                 const int32_t id = seed_ids[s0 + r];
-                const bool q = ctx->quirk[id] != 0;
-                const int bv = q ? lcsgpu::quirk_h_class(ctx->lens[id]) : target[lcsgpu::h_class(ctx->lens[id])];
-                const int key = bv * 2 + (q ? 1 : 0);
-                if (index_of[key] < 0) {
-                    index_of[key] = (int)buckets.size();
-                    buckets.push_back(Bucket{bv, q, {}, {}, {}, {}, {}, 0});
-                }
-                Bucket& b = buckets[index_of[key]];
-                b.ref_id.push_back(id);
-                b.ref_col0.push_back((int32_t)(pc.c0 - C0));
-                b.ref_piece.push_back((int32_t)(p - p0));
-                b.ref_out0.push_back(out_at + r * w);
+                const uint8_t c = ctx->ref_class[(size_t)id];
+                const bool q = (c & 0x80) != 0;
+                refs.push_back(JobRef{id, (int32_t)(p - p0), (int32_t)(pc.c0 - C0), pc.c1 - C0, out_at + r * w,
+                                      q ? 0.0 : (double)((w + 255) / 256) / lcsgpu::refs_per_block_for(c, false, 1, 1), c,
+                                      (uint8_t)(q ? lcsgpu::quirk_h_class(ctx->lens[id]) : 0), false});
             }
             out_at += ns * w;
         }
-        size_t plan = 0;
-        const size_t o_table = plan; plan += a256((size_t)np * sizeof(lcsgpu::AssignPiece));
-        std::vector<size_t> o_id(buckets.size()), o_c0(buckets.size()), o_out(buckets.size()), o_job(buckets.size());
-        for (size_t bi = 0; bi < buckets.size(); ++bi) {
-            Bucket& b = buckets[bi];
-            const size_t nr = b.ref_id.size();
-            const int R = b.refs_per_wg = lcsgpu::refs_per_block_for(b.bv, b.quirk, (long)nr, (long)std::max<int64_t>(1, nc / 256 / std::max(1, np)));
-            for (size_t k0 = 0; k0 < nr;) {
-                size_t k1 = k0 + 1;
-                while (k1 < nr && k1 - k0 < (size_t)R && b.ref_piece[k1] == b.ref_piece[k0]) ++k1;
-                const lcsgpu::AssignPiece& tp = table[(size_t)b.ref_piece[k0]];
-                for (int32_t c = tp.col0; c < tp.col0 + tp.n_cols; c += 256) b.jobs.push_back(make_int4((int)k0, (int)(k1 - k0), c, tp.col0 + tp.n_cols));
-                k0 = k1;
-            }
-            if (b.jobs.size() > 0x7fffffffu) return fail(LCSGPU_E_INVALID, "batch too large");
-            o_id[bi] = plan; plan += a256(nr * 4);
-            o_c0[bi] = plan; plan += a256(nr * 4);
-            o_out[bi] = plan; plan += a256(nr * 8);
-            o_job[bi] = plan; plan += a256(b.jobs.size() * sizeof(int4));
-        }
-        if (L.plan_in_flight) {
-            HIP_TRY(hipStreamSynchronize(L.stream));
-            L.plan_in_flight = false;
-        }
-        HIP_TRY(L.h_plan.reserve(plan));
-        HIP_TRY(L.d_plan.reserve(plan));
-        char* h = (char*)L.h_plan.p;
-        memcpy(h + o_table, table.data(), (size_t)np * sizeof(lcsgpu::AssignPiece));
-        for (size_t bi = 0; bi < buckets.size(); ++bi) {
-            const Bucket& b = buckets[bi];
-            memcpy(h + o_id[bi], b.ref_id.data(), b.ref_id.size() * 4);
-            memcpy(h + o_c0[bi], b.ref_col0.data(), b.ref_col0.size() * 4);
-            memcpy(h + o_out[bi], b.ref_out0.data(), b.ref_out0.size() * 8);
-            memcpy(h + o_job[bi], b.jobs.data(), b.jobs.size() * sizeof(int4));
-        }
-        HIP_TRY(hipMemcpyAsync(L.d_plan.p, h, plan, hipMemcpyHostToDevice, L.stream));
-        L.plan_in_flight = true;
+        if (!plan_jobs(refs, (long)std::max<int64_t>(1, nc / 256 / std::max(1, np)), lcsgpu::refs_per_block_for, buckets))
+            return fail(LCSGPU_E_INVALID, "batch too large");
+        PlanLayout lay;
+        int rc = stage_job_tables(L, buckets, table.data(), (size_t)np * sizeof(lcsgpu::AssignPiece), lay);
+        if (rc) return rc;
         // columns, distances, assignments of the launch
         const size_t o_cols = 0, o_dist = o_cols + a256((size_t)nc * 4), o_assign = o_dist + a256((size_t)nc * 4), work = o_assign + a256((size_t)nc * 4);
         HIP_TRY(L.d_work.reserve(work));
-        int rc = reserve_big(ctx, L.d_out, (size_t)out_at * elem, "assign_seeds_batch rectangles");
+        rc = reserve_big(ctx, L.d_out, (size_t)out_at * elem, "assign_seeds_batch rectangles");
         if (rc) return rc;
         char* base = (char*)L.d_work.p;
         HIP_TRY(hipMemcpyAsync(base + o_cols, col_ids + C0, (size_t)nc * 4, hipMemcpyHostToDevice, L.stream));
-        L.last_launches = 0;
-        HIP_TRY(hipEventRecord(L.ev_start, L.stream));
-        for (size_t bi = 0; bi < buckets.size(); ++bi) {
-            const Bucket& b = buckets[bi];
-            if (b.jobs.empty()) continue;
-            RowsArgs a{};
-            a.tiles = (const uint8_t*)ctx->d_tiles.p;
-            a.tile_base = (const uint64_t*)ctx->d_tile_base.p;
-            a.lens = (const uint32_t*)ctx->d_lens.p;
-            a.masks = (const uint64_t*)ctx->d_masks.p;
-            a.mask_base = (const uint64_t*)ctx->d_mask_base.p;
-            a.n_refs = (int32_t)b.ref_id.size();
-            char* d = (char*)L.d_plan.p;
-            a.ref_ids = (const int32_t*)(d + o_id[bi]);
-            a.ref_rows = nullptr;
-            a.ref_col0 = (const int32_t*)(d + o_c0[bi]);
-            a.ref_out0 = (const int64_t*)(d + o_out[bi]);
-            a.jobs = (const int4*)(d + o_job[bi]);
-            a.col_ids = (const int32_t*)(base + o_cols);
-            a.n_cols = (int32_t)nc;
-            a.out = L.d_out.p;
-            a.elem_size = elem;
-            a.mode = lcsgpu::MODE_RECT;
-            a.refs_per_block = b.refs_per_wg;
-            HIP_TRY(lcsgpu::launch_rows(b.bv, b.quirk, a, (int)b.jobs.size(), 1, L.stream));
-            trace_lcs_launch(b.bv, b.quirk, a, (long)b.jobs.size());
-            ++L.last_launches;
-        }
-        HIP_TRY(hipEventRecord(L.ev_stop, L.stream));
-        L.timing_valid = true;
-        HIP_TRY(lcsgpu::launch_assign_seeds_batch(L.d_out.p, elem, (const lcsgpu::AssignPiece*)((char*)L.d_plan.p + o_table), np,
+        rc = launch_job_tables(ctx, L, buckets, lay, lcsgpu::MODE_RECT, (const int32_t*)(base + o_cols), nc, elem);
+        if (rc) return rc;
+        HIP_TRY(lcsgpu::launch_assign_seeds_batch(L.d_out.p, elem, (const lcsgpu::AssignPiece*)L.d_plan.p /* the plan buffer's first table */, np,
                                                   (const int32_t*)L.d_draws.p, (const int32_t*)(base + o_cols), nc, (const uint32_t*)ctx->d_lens.p,
                                                   (const float*)ctx->d_powf.p, distance_kind, (float*)(base + o_dist), (int32_t*)(base + o_assign), L.stream));
         HIP_TRY(hipMemcpyAsync(dist + C0, base + o_dist, (size_t)nc * 4, hipMemcpyDeviceToHost, L.stream));
@@ -843,8 +704,7 @@ static int clarans_batch_impl(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t
 {
     if (!ctx) return fail(LCSGPU_E_INVALID, "NULL ctx");
     if (ctx->n < 0) return fail(LCSGPU_E_STATE, "no sequence set uploaded");
-    if (distance_kind != LCSGPU_DIST_INDEL_DIV_LCS && distance_kind != LCSGPU_DIST_INDEL075_DIV_LCS)
-        return fail(LCSGPU_E_INVALID, "unknown distance kind %d", distance_kind);
+    if (!valid_kind(distance_kind)) return fail(LCSGPU_E_INVALID, "unknown distance kind %d", distance_kind);
     if (n_jobs < 0 || num_local < 1 || n_fixed < 0) return fail(LCSGPU_E_INVALID, "bad CLARANS batch");
     if (n_jobs == 0) return LCSGPU_OK;
     if (!ids || !offsets || !n_medoids || !medoids_out) return fail(LCSGPU_E_INVALID, "NULL argument");
@@ -955,7 +815,6 @@ static int clarans_batch_impl(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t
         lcs_launches = g_last.launches;
     }
     // the samples' buffers, one allocation
-    auto a256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const int n_live = (int)live.size();
     const int64_t n_total = offsets[n_jobs];
     size_t at = 0;
@@ -1193,28 +1052,48 @@ static int clarans_batch_impl(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t
     return LCSGPU_OK;
 }
 
-// the C-ABI's boundary: no exception leaves it (a std::bad_alloc of the host-side tables would end in std::terminate)
-static int clarans_batch_guarded(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* offsets, int32_t n_jobs, int distance_kind,
-                                 const int32_t* n_medoids, int32_t n_fixed, float explore_fraction, int32_t num_local, int32_t* medoids_out,
-                                 bool allow_large)
+extern "C" { // every call through `guarded`
+
+int lcsgpu_lcs_triangles_batch(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* group_offsets, int32_t n_groups,
+                               void* out, int elem_size)
 {
-    try {
-        return clarans_batch_impl(ctx, ids, offsets, n_jobs, distance_kind, n_medoids, n_fixed, explore_fraction, num_local, medoids_out, allow_large);
-    } catch (const std::exception& e) {
-        return fail(LCSGPU_E_NOMEM, "CLARANS batch: %s", e.what());
-    }
+    return guarded("lcs_triangles_batch", lcs_triangles_batch_impl, ctx, ids, group_offsets, n_groups, out, elem_size);
+}
+
+int lcsgpu_mst_prim_batch(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* group_offsets, int32_t n_groups, int distance_kind,
+                          lcsgpu_mst_edge* out_edges)
+{
+    return guarded("batched MST", mst_prim_batch_impl, ctx, ids, group_offsets, n_groups, distance_kind, out_edges);
+}
+
+int lcsgpu_upgma_batch(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* group_offsets, int32_t n_groups, int distance_kind,
+                       int modified, int32_t* out_left, int32_t* out_right, int32_t* out_status)
+{
+    return guarded("batched UPGMA", upgma_batch_impl, ctx, ids, group_offsets, n_groups, distance_kind, modified, out_left, out_right, out_status);
+}
+
+int lcsgpu_assign_seeds(lcsgpu_ctx* ctx, const int32_t* seed_ids, int32_t n_seeds, const int32_t* col_ids,
+                        int32_t n_cols, int distance_kind, int32_t first_k, float* dist, int32_t* assign)
+{
+    return guarded("assign_seeds", assign_seeds_impl, ctx, seed_ids, n_seeds, col_ids, n_cols, distance_kind, first_k, dist, assign);
+}
+
+int lcsgpu_assign_seeds_batch(lcsgpu_ctx* ctx, const int32_t* seed_ids, const int64_t* seed_offsets, const int32_t* col_ids,
+                              const int64_t* col_offsets, int32_t n_jobs, int distance_kind, float* dist, int32_t* assign)
+{
+    return guarded("assign_seeds_batch", assign_seeds_batch_impl, ctx, seed_ids, seed_offsets, col_ids, col_offsets, n_jobs, distance_kind, dist, assign);
 }
 
 int lcsgpu_clarans_batch(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* offsets, int32_t n_jobs, int distance_kind,
                          const int32_t* n_medoids, int32_t n_fixed, float explore_fraction, int32_t num_local, int32_t* medoids_out)
 {
-    return clarans_batch_guarded(ctx, ids, offsets, n_jobs, distance_kind, n_medoids, n_fixed, explore_fraction, num_local, medoids_out, false);
+    return guarded("CLARANS batch", clarans_batch_impl, ctx, ids, offsets, n_jobs, distance_kind, n_medoids, n_fixed, explore_fraction, num_local, medoids_out, false);
 }
 
 int lcsgpu_clarans_large_batch(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* offsets, int32_t n_jobs, int distance_kind,
                                const int32_t* n_medoids, int32_t n_fixed, float explore_fraction, int32_t num_local, int32_t* medoids_out)
 {
-    return clarans_batch_guarded(ctx, ids, offsets, n_jobs, distance_kind, n_medoids, n_fixed, explore_fraction, num_local, medoids_out, true);
+    return guarded("CLARANS batch", clarans_batch_impl, ctx, ids, offsets, n_jobs, distance_kind, n_medoids, n_fixed, explore_fraction, num_local, medoids_out, true);
 }
 
 int lcsgpu_clarans(lcsgpu_ctx* ctx, const int32_t* ids, int32_t n_ids, int distance_kind, int32_t n_medoids,
@@ -1222,7 +1101,7 @@ int lcsgpu_clarans(lcsgpu_ctx* ctx, const int32_t* ids, int32_t n_ids, int dista
 {
     if (!ids || !medoids_out || n_ids < 1) return fail(LCSGPU_E_INVALID, "bad sample / output");
     const int64_t offsets[2] = {0, n_ids};
-    return clarans_batch_guarded(ctx, ids, offsets, 1, distance_kind, &n_medoids, n_fixed, explore_fraction, num_local, medoids_out, false);
+    return lcsgpu_clarans_batch(ctx, ids, offsets, 1, distance_kind, &n_medoids, n_fixed, explore_fraction, num_local, medoids_out);
 }
 
 int lcsgpu_clarans_large(lcsgpu_ctx* ctx, const int32_t* ids, int32_t n_ids, int distance_kind, int32_t n_medoids,
@@ -1230,7 +1109,7 @@ int lcsgpu_clarans_large(lcsgpu_ctx* ctx, const int32_t* ids, int32_t n_ids, int
 {
     if (!ids || !medoids_out || n_ids < 1) return fail(LCSGPU_E_INVALID, "bad sample / output");
     const int64_t offsets[2] = {0, n_ids};
-    return clarans_batch_guarded(ctx, ids, offsets, 1, distance_kind, &n_medoids, n_fixed, explore_fraction, num_local, medoids_out, true);
+    return lcsgpu_clarans_large_batch(ctx, ids, offsets, 1, distance_kind, &n_medoids, n_fixed, explore_fraction, num_local, medoids_out);
 }
 
 } // extern "C"

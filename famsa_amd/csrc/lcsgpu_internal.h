@@ -24,6 +24,7 @@
 
 #include "../../include/lcsgpu.h"
 #include "lcs_kernels.h"
+#include "job_plan.h"
 
 namespace lcsgpu_impl {
 
@@ -195,6 +196,23 @@ struct ComputeGate {
         }
         cv.notify_all();
     }
+};
+// A bulk LCS call's shared hold: from its first launch until its kernels have run; the plan is made before, the results
+// travel after.
+struct GateHold {
+    ComputeGate& g;
+    bool held = false;
+    void lock()
+    {
+        g.lock_shared();
+        held = true;
+    }
+    void release()
+    {
+        if (held) g.unlock_shared();
+        held = false;
+    }
+    ~GateHold() { release(); }
 };
 
 struct lcsgpu_ctx {
@@ -378,9 +396,9 @@ void text_release(lcsgpu_ctx* ctx);
 int run_rows(lcsgpu_ctx* ctx, Lane& L, int mode, const int32_t* ref_ids, int32_t ref_begin, int32_t n_refs,
              const int32_t* col_ids, int32_t col_begin, int32_t n_cols, void* d_out, int64_t ld,
              int64_t out_offset, int elem_size, int64_t first_row = 0, const lcsgpu::FuseArgs* fuse = nullptr);
-// which instantiation the refs of half-word class h run in (target[h] >= h), given wgs[h] = the workgroups class h would
-// have on its own, h = 1 .. 64: small neighbouring classes share a launch (lcsgpu_api.hip)
-void merge_small_classes(const double* wgs, int* target);
+// the uploaded set's tables (tiles, tile_base, lens, masks, mask_base) in an otherwise empty RowsArgs: where every planner starts
+lcsgpu::RowsArgs rows_args_of_set(const lcsgpu_ctx* ctx);
+inline bool valid_kind(int kind) { return kind == LCSGPU_DIST_INDEL_DIV_LCS || kind == LCSGPU_DIST_INDEL075_DIV_LCS; }
 // After a host-memory call has been synchronised: account its kernel time.
 void finish_host_call(lcsgpu_ctx* ctx, Lane& L);
 // a host-memory call that keeps its own events (lcsgpu_text.hip): this thread's answer to lcsgpu_last_kernel_ms

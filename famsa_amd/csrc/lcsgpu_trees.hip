@@ -282,8 +282,6 @@ int order_edges_like_prim(lcsgpu_mst_edge* edges, int32_t n)
 
 extern "C" {
 
-static bool valid_kind(int kind) { return kind == LCSGPU_DIST_INDEL_DIV_LCS || kind == LCSGPU_DIST_INDEL075_DIV_LCS; }
-
 int lcsgpu_mst_shard_begin(lcsgpu_ctx* ctx, void* d_triangle, int elem_size, int32_t row_begin, int32_t row_end,
                            int distance_kind)
 {

@@ -94,4 +94,38 @@ struct GroupUpgmaArgs {
 // the launch pair of a slice: the squares with the rows' initial keys, then the merges
 hipError_t launch_group_upgma(const GroupUpgmaArgs& a, hipStream_t stream);
 
+// ---- neighbour joining of many small groups: one workgroup per group (nj_group_kernels.hip) ----
+constexpr int NJ_GROUP_MAX_MEMBERS = 2048; // = LCSGPU_NJ_BATCH_MAX_MEMBERS: a group costs m^3 / 6 evaluations of q on ONE CU
+constexpr int NJ_GROUP_WIDE_AT = 200;      // groups from this many members on run in 1024 threads, smaller ones in 256 (profiles/batch_nj.txt)
+struct GroupNjJob {
+    int64_t tri0;  // element offset of the group's packed LCS triangle in the launch's triangle buffer
+    int64_t f0;    // ... of its packed float triangle (same layout) in the launch's float buffer
+    int64_t node0; // record offset of its m - 1 internal nodes
+    int32_t id0;   // position of its first member in the concatenated id list
+    int32_t m;     // members, 2 .. NJ_GROUP_MAX_MEMBERS
+    int32_t group; // the caller's list number: where its status goes
+    int32_t pad;
+};
+struct GroupNjArgs {
+    const uint16_t* tri;    // the groups' packed triangles (ref = the later member)
+    float* dist;            // the launch's float triangles
+    const GroupNjJob* jobs; // the launch's jobs, longest first
+    const int64_t* row0;    // [n_jobs + 1] prefix sums of m over the launch's jobs
+    const int32_t* ids;     // the concatenated id lists
+    const uint32_t* lens;
+    const float* pow_f32;   // (float) pow(i, 0.75)
+    float* row_sum;         // [total_rows] every row's initial sum of distances
+    int32_t* left;
+    int32_t* right;
+    int32_t* status;        // [the call's groups] 1 = no q below FLT_MAX at some merge; zeroed before the launch
+    int64_t total_rows;     // row0[n_jobs]
+    int32_t n_jobs, kind, max_m;
+    int32_t n_wide;         // the first n_wide jobs run in 1024 threads, the others in 256
+    int32_t narrow_m;       // members of job n_wide, the longest of the others
+};
+// the launches of a slice: the float triangles with the rows' initial sums, then the merges
+hipError_t launch_group_nj(const GroupNjArgs& a, hipStream_t stream);
+// launches launch_group_nj makes for these arguments (the call's accounting)
+int group_nj_launches(const GroupNjArgs& a);
+
 } // namespace lcsgpu

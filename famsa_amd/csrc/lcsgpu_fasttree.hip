@@ -516,6 +516,124 @@ static int upgma_batch_impl(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* 
     });
 }
 
+// Neighbour joining of many id lists: the lists' triangles by the launches of lcsgpu_lcs_triangles_batch, then per slice of
+// lists the launches of nj_group_kernels.hip: the float triangles with the rows' initial sums, and a workgroup per list
+// that runs the list's merges, longest lists first.
+static int nj_batch_impl(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* group_offsets, int32_t n_groups, int distance_kind,
+                         int32_t* out_left, int32_t* out_right, int32_t* out_status)
+{
+    // everything that refuses comes first: nothing is computed, the outputs stay as they are
+    std::vector<lcsgpu::GroupNjJob> jobs;
+    int64_t n_nodes = 0;
+    int rc = check_groups(
+        ctx, ids, group_offsets, n_groups, distance_kind,
+        [&](int32_t g, int64_t m) {
+            if (m > LCSGPU_NJ_BATCH_MAX_MEMBERS)
+                return fail(LCSGPU_E_UNSUPPORTED, "group %d has %lld members: the batched NJ handles at most %d (use lcsgpu_nj)", g,
+                            (long long)m, LCSGPU_NJ_BATCH_MAX_MEMBERS);
+            if (m >= 2) {
+                jobs.push_back(lcsgpu::GroupNjJob{(int64_t)g /* the group, until its triangle's place is known */, 0, n_nodes,
+                                                  (int32_t)group_offsets[g], (int32_t)m, g, 0});
+                n_nodes += m - 1;
+            }
+            return 0;
+        },
+        [&](int32_t id) {
+            // (orientation-sensitive members are served: the triangle's orientation, ref = the later member, IS
+            // calculateDistanceMatrix's)
+            if (ctx->lens[(size_t)id] > 65535)
+                return fail(LCSGPU_E_UNSUPPORTED, "sequence %d is longer than 65535 residues: the batched NJ keeps 16-bit LCS values", id);
+            return 0;
+        });
+    if (rc || n_groups == 0) return rc;
+    if (!out_status) return fail(LCSGPU_E_INVALID, "NULL out_status");
+    if (n_nodes > 0 && (!out_left || !out_right)) return fail(LCSGPU_E_INVALID, "NULL out_left / out_right");
+    if (jobs.empty()) {
+        std::fill(out_status, out_status + n_groups, 0);
+        return LCSGPU_OK;
+    }
+    // the float triangles of a slice: at most this many MB (a slice always holds at least one group)
+    const int slice_mb = std::max(1, tune_int("nj_group_mb", 2048));
+    // 256 threads below NJ_GROUP_WIDE_AT members, 1024 from there on (profiles/batch_nj.txt); nj_group_threads forces one
+    // (neither is cached: tests switch them inside one process)
+    const int forced_threads = tune_int("nj_group_threads", 0);
+    const int wide_at = forced_threads == 256 ? LCSGPU_NJ_BATCH_MAX_MEMBERS + 1 : forced_threads == 1024 ? 0 : lcsgpu::NJ_GROUP_WIDE_AT;
+
+    GroupCall call(ctx);
+    Lane& L = call.L;
+    rc = call.triangles(ids, group_offsets, n_groups, "NJ", jobs);
+    if (rc) return rc;
+    const int64_t n_total = group_offsets[n_groups];
+    struct Slice { size_t job0, n_jobs, row_at; int64_t rows, elems; int32_t max_m, n_wide, narrow_m; };
+    std::vector<Slice> slices;
+    std::vector<int64_t> row0; // per slice: the prefix sums of m over its jobs, one slice after the other
+    const int64_t slice_elems = (int64_t)slice_mb * (1 << 20) / 4;
+    int64_t max_elems = 0, max_rows = 0;
+    for (size_t j = 0; j < jobs.size(); ++j) {
+        lcsgpu::GroupNjJob& job = jobs[j];
+        // n_wide / narrow_m below, and the LDS of a launch (its first job's m), rely on GroupCall::triangles' order
+        if (j > 0 && job.m > jobs[j - 1].m) return fail(LCSGPU_E_STATE, "the batched NJ's jobs are not longest first");
+        const int64_t elems = (int64_t)job.m * (job.m - 1) / 2;
+        if (slices.empty() || slices.back().elems + elems > slice_elems) {
+            slices.push_back(Slice{j, 0, row0.size(), 0, 0, job.m, 0, 0});
+            row0.push_back(0);
+        }
+        Slice& s = slices.back();
+        job.f0 = s.elems;
+        s.elems += elems;
+        s.rows += job.m;
+        if (job.m >= wide_at) ++s.n_wide; // (longest first: the wide jobs are the slice's first)
+        else if (s.narrow_m == 0) s.narrow_m = job.m;
+        ++s.n_jobs;
+        row0.push_back(s.rows);
+        max_elems = std::max(max_elems, s.elems);
+        max_rows = std::max(max_rows, s.rows);
+    }
+    const size_t o_jobs = 0, o_row0 = o_jobs + a256(jobs.size() * sizeof(lcsgpu::GroupNjJob)), o_ids = o_row0 + a256(row0.size() * 8),
+                 o_left = o_ids + a256((size_t)n_total * 4), o_right = o_left + a256((size_t)n_nodes * 4),
+                 o_status = o_right + a256((size_t)n_nodes * 4), o_sum = o_status + a256((size_t)n_groups * 4),
+                 o_dist = o_sum + a256((size_t)max_rows * 4), total = o_dist + a256((size_t)max_elems * 4);
+    rc = reserve_big(ctx, L.d_work, total, "the batched NJ's tables and float triangles");
+    if (rc) return rc;
+    char* base = (char*)L.d_work.p;
+    HIP_TRY(hipMemcpyAsync(base + o_jobs, jobs.data(), jobs.size() * sizeof(lcsgpu::GroupNjJob), hipMemcpyHostToDevice, L.stream));
+    HIP_TRY(hipMemcpyAsync(base + o_row0, row0.data(), row0.size() * 8, hipMemcpyHostToDevice, L.stream));
+    HIP_TRY(hipMemcpyAsync(base + o_ids, ids, (size_t)n_total * 4, hipMemcpyHostToDevice, L.stream));
+    HIP_TRY(hipMemsetAsync(base + o_status, 0, (size_t)n_groups * 4, L.stream));
+    int launches = 0;
+    for (const Slice& s : slices) {
+        lcsgpu::GroupNjArgs a{};
+        a.tri = (const uint16_t*)L.d_out.p;
+        a.dist = (float*)(base + o_dist);
+        a.jobs = (const lcsgpu::GroupNjJob*)(base + o_jobs) + s.job0;
+        a.row0 = (const int64_t*)(base + o_row0) + s.row_at;
+        a.ids = (const int32_t*)(base + o_ids);
+        a.lens = (const uint32_t*)ctx->d_lens.p;
+        a.pow_f32 = (const float*)ctx->d_powf.p;
+        a.row_sum = (float*)(base + o_sum);
+        a.left = (int32_t*)(base + o_left);
+        a.right = (int32_t*)(base + o_right);
+        a.status = (int32_t*)(base + o_status);
+        a.total_rows = s.rows;
+        a.n_jobs = (int32_t)s.n_jobs;
+        a.kind = distance_kind;
+        a.max_m = s.max_m;
+        a.n_wide = s.n_wide;
+        a.narrow_m = s.narrow_m;
+        if (const hipError_t e = lcsgpu::launch_group_nj(a, L.stream))
+            return fail(LCSGPU_E_HIP, "the batched NJ's launch failed: %s", hipGetErrorString(e));
+        launches += lcsgpu::group_nj_launches(a);
+    }
+    return call.finish(launches, [&] { // left | right | status are neighbours in the work buffer: one copy, then three
+        std::vector<char> back(o_sum - o_left);
+        HIP_TRY(hipMemcpy(back.data(), base + o_left, back.size(), hipMemcpyDeviceToHost));
+        memcpy(out_left, back.data(), (size_t)n_nodes * 4);
+        memcpy(out_right, back.data() + (o_right - o_left), (size_t)n_nodes * 4);
+        memcpy(out_status, back.data() + (o_status - o_left), (size_t)n_groups * 4);
+        return LCSGPU_OK;
+    });
+}
+
 static int assign_seeds_impl(lcsgpu_ctx* ctx, const int32_t* seed_ids, int32_t n_seeds, const int32_t* col_ids, int32_t n_cols,
                              int distance_kind, int32_t first_k, float* dist, int32_t* assign)
 {
@@ -1070,6 +1188,12 @@ int lcsgpu_upgma_batch(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* group
                        int modified, int32_t* out_left, int32_t* out_right, int32_t* out_status)
 {
     return guarded("batched UPGMA", upgma_batch_impl, ctx, ids, group_offsets, n_groups, distance_kind, modified, out_left, out_right, out_status);
+}
+
+int lcsgpu_nj_batch(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* group_offsets, int32_t n_groups, int distance_kind,
+                    int32_t* out_left, int32_t* out_right, int32_t* out_status)
+{
+    return guarded("batched NJ", nj_batch_impl, ctx, ids, group_offsets, n_groups, distance_kind, out_left, out_right, out_status);
 }
 
 int lcsgpu_assign_seeds(lcsgpu_ctx* ctx, const int32_t* seed_ids, int32_t n_seeds, const int32_t* col_ids,

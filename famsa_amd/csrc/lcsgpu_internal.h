@@ -36,7 +36,9 @@ int fail(int code, const char* fmt, ...);
 // drawn for a sample shape before its first launch, 65536), assign_batch_kb (LCS rectangles of one launch of the batched seed
 // assignment, 2 GB), upgma_spare (spare slots of the UPGMA matrix, n / 10), mst_batch_square (1, the default: lcsgpu_mst_prim_batch
 // expands every group's triangle to a square first; 0: it reads the packed triangles -- measurements), upgma_group_mb
-// (the float squares of one launch pair of lcsgpu_upgma_batch, 4096 MB; a slice always holds one group), lcs_plan_trace (1: every
+// (the float squares of one launch pair of lcsgpu_upgma_batch, 4096 MB; a slice always holds one group), nj_group_mb (the
+// float triangles of one slice of lcsgpu_nj_batch, 2048 MB) and nj_group_threads (256 | 1024: every list's workgroup gets that
+// many threads instead of the size's own choice) -- both read at every call --, lcs_plan_trace (1: every
 // LCS launch is named on stderr with the plan it got -- a test aid, read at every call)
 int tune_int(const char* key, int dflt);
 // LCSGPU_TUNE lcs_plan_trace=1: one line per LCS launch, "lcsgpu: lcs launch h=<half-words, 0 = the long kernel> quirk=<0|1>

@@ -10,6 +10,8 @@
 #include <stdexcept>
 #include <thread>
 
+#include "../../include/lcsgpu.h"
+
 namespace famsa_host {
 
 namespace {
@@ -98,8 +100,8 @@ private:
 };
 
 // A file's slice of a chunk as the tree builders see it: ids 0 .. m - 1 = the file's sorted unique working order.  Prim's
-// edges come from the chunk's lcsgpu_mst_prim_batch, UPGMA's node records from its lcsgpu_upgma_batch, the triangle from its
-// lcsgpu_lcs_triangles_batch; nothing is computed here.
+// edges come from the chunk's lcsgpu_mst_prim_batch, UPGMA's node records from its lcsgpu_upgma_batch, NJ's from its
+// lcsgpu_nj_batch, the triangle from its lcsgpu_lcs_triangles_batch; nothing is computed here.
 class SliceLcsSource : public LcsSource {
 public:
     SliceLcsSource(const SeqSet& s, const std::vector<int>& in_of, bool sensitive) : s_(s), in_of_(in_of), sensitive_(sensitive) {}
@@ -107,11 +109,12 @@ public:
     const MstEdge* edges = nullptr;  // its m - 1 MST records, or NULL
     int edges_kind = -1;
     bool edges_triangle_orientation = false;
-    const int32_t* left = nullptr;   // its m - 1 UPGMA node records, or NULL
+    const int32_t* left = nullptr;   // its m - 1 UPGMA or NJ node records, or NULL
     const int32_t* right = nullptr;
     int nodes_kind = -1;
     bool nodes_modified = false;
-    bool nodes_failed = false;       // the device found no finite nearest neighbour in this file
+    bool nodes_nj = false;           // the records are neighbour joining's
+    bool nodes_failed = false;       // the device found no finite nearest neighbour (UPGMA) / no finite q (NJ) in this file
 
     int n() const override { return (int)in_of_.size(); }
     uint32_t length(int i) const override { return s_.length((size_t)in_of_[(size_t)i]); }
@@ -138,10 +141,19 @@ public:
     }
     bool upgma_nodes(int distance_kind, bool modified, std::vector<int32_t>& l, std::vector<int32_t>& r) override
     {
-        if (!left || !right || distance_kind != nodes_kind || modified != nodes_modified) return false;
+        if (!left || !right || nodes_nj || distance_kind != nodes_kind || modified != nodes_modified) return false;
         if (nodes_failed) // what the host builder says for such a file (trees.cpp)
             throw std::runtime_error("UPGMA: no finite nearest neighbour (a pair with LCS 0?) -- the reference's "
                                      "algorithm is undefined for this input");
+        l.assign(left, left + (n() > 0 ? n() - 1 : 0));
+        r.assign(right, right + (n() > 0 ? n() - 1 : 0));
+        return true;
+    }
+    bool nj_nodes(int distance_kind, std::vector<int32_t>& l, std::vector<int32_t>& r) override
+    {
+        if (!left || !right || !nodes_nj || distance_kind != nodes_kind) return false;
+        if (nodes_failed) // what the host builder says for such a file (trees.cpp, nj_tree)
+            throw std::runtime_error("NJ: no finite q (a pair with LCS 0?) -- the reference's result is degenerate for this input");
         l.assign(left, left + (n() > 0 ? n() - 1 : 0));
         r.assign(right, right + (n() > 0 ? n() - 1 : 0));
         return true;
@@ -291,7 +303,7 @@ std::vector<BatchResult> guide_trees_newick_gpu(const std::vector<BatchJob>& job
     struct ChunkData {
         std::vector<LcsSource::MstEdge> edges[4]; // by (triangle orientation, distance kind)
         LcsBuf tri;
-        std::vector<int32_t> left[4], right[4], status[4]; // UPGMA by (modified, distance kind)
+        std::vector<int32_t> left[6], right[6], status[6]; // UPGMA by (modified, distance kind), then NJ by distance kind
     };
     auto run_chunk = [&](const std::vector<size_t>& files) {
         GpuLcsSource* src = the_engine();
@@ -333,14 +345,15 @@ std::vector<BatchResult> guide_trees_newick_gpu(const std::vector<BatchJob>& job
 
             auto data = std::make_shared<ChunkData>();
             std::vector<char> sensitive(files.size(), 0);
-            // which of the nine requests serves the file: 0 .. 3 = Prim's edges, 4 = the triangles, 5 .. 8 = UPGMA's node records
+            // which of the eleven requests serves the file: 0 .. 3 = Prim's edges, 4 = the triangles, 5 .. 8 = UPGMA's node
+            // records, 9 .. 10 = NJ's
             std::vector<int> list_of(files.size(), -1);
             std::vector<size_t> at(files.size(), 0);        // where its records / its triangle start in that request's result
             std::vector<int> group_of(files.size(), 0);     // its list number inside the request
-            std::vector<std::vector<int>> ids(9);
-            std::vector<std::vector<int64_t>> offs(9, std::vector<int64_t>{0});
-            std::vector<size_t> filled(9, 0);
-            const bool upgma_on_host = host_test("batch_upgma_host");
+            std::vector<std::vector<int>> ids(11);
+            std::vector<std::vector<int64_t>> offs(11, std::vector<int64_t>{0});
+            std::vector<size_t> filled(11, 0);
+            const bool upgma_on_host = host_test("batch_upgma_host"), nj_on_host = host_test("batch_nj_host");
             for (size_t k = 0; k < files.size(); ++k) {
                 const size_t i = files[k];
                 const Loaded& f = *loaded[i];
@@ -358,6 +371,11 @@ std::vector<BatchResult> guide_trees_newick_gpu(const std::vector<BatchJob>& job
                 if (is_mst(opt.method)) list = (opt.method == GT::SLINK ? 2 : 0) + (opt.dist == Distance::indel075_div_lcs ? 1 : 0);
                 else if (is_upgma(opt.method) && !upgma_on_host)
                     list = 5 + (opt.method == GT::UPGMA_modified ? 2 : 0) + (opt.dist == Distance::indel075_div_lcs ? 1 : 0);
+                // -gt nj: every size a chunk takes goes to the device.  Files per second against the host builders of the commit
+                // before, in alternating runs (profiles/batch_nj.txt): 3119 against 2011 at 50 members, 1339 against 1036 at
+                // 200, 280 against 59 at 1000 -- no size is behind, so there is no lower threshold.
+                else if (opt.method == GT::NJ && !nj_on_host && m <= LCSGPU_NJ_BATCH_MAX_MEMBERS) // (above: the routing limit was lifted)
+                    list = 9 + (opt.dist == Distance::indel075_div_lcs ? 1 : 0);
                 else list = 4;
                 list_of[k] = list;
                 group_of[k] = (int)offs[(size_t)list].size() - 1;
@@ -375,6 +393,10 @@ std::vector<BatchResult> guide_trees_newick_gpu(const std::vector<BatchJob>& job
                 if (offs[(size_t)list].size() > 1)
                     src->upgma_nodes_batch(ids[(size_t)list].data(), offs[(size_t)list].data(), (int)offs[(size_t)list].size() - 1,
                                            (list - 5) & 1, list >= 7, data->left[list - 5], data->right[list - 5], data->status[list - 5]);
+            for (int list = 9; list < 11; ++list)
+                if (offs[(size_t)list].size() > 1)
+                    src->nj_nodes_batch(ids[(size_t)list].data(), offs[(size_t)list].data(), (int)offs[(size_t)list].size() - 1, list - 9,
+                                        data->left[list - 5], data->right[list - 5], data->status[list - 5]);
             const double t2 = now_s();
             {
                 std::lock_guard<std::mutex> lk(tot_mu);
@@ -400,7 +422,8 @@ std::vector<BatchResult> guide_trees_newick_gpu(const std::vector<BatchJob>& job
                             view.left = data->left[list - 5].data() + where;
                             view.right = data->right[list - 5].data() + where;
                             view.nodes_kind = (list - 5) & 1;
-                            view.nodes_modified = list >= 7;
+                            view.nodes_modified = list == 7 || list == 8;
+                            view.nodes_nj = list >= 9;
                             view.nodes_failed = data->status[list - 5][(size_t)group] != 0;
                         } else if (list >= 0) {
                             view.edges = data->edges[list].data() + where;
@@ -415,7 +438,8 @@ std::vector<BatchResult> guide_trees_newick_gpu(const std::vector<BatchJob>& job
                             std::lock_guard<std::mutex> lk(tot_mu);
                             tot.newick_s += now_s() - c0;
                             ++tot.in_chunks;
-                            if (list >= 5) ++tot.device_upgma;
+                            if (list >= 9) ++tot.device_nj;
+                            else if (list >= 5) ++tot.device_upgma;
                         }
                         finish(i, std::move(r));
                     } catch (const std::exception& e) {

@@ -3,9 +3,10 @@
 // all launch latency to the one-file path (eight Boruvka rounds of five or more launches each, one busy CU).  Here the
 // files are loaded and sorted on the host's worker threads, packed into CHUNKS, and a chunk's trees are made together:
 // one upload of the chunk's records, then one lcsgpu_mst_prim_batch (-gt sl / slink: a workgroup per file), one
-// lcsgpu_upgma_batch (-gt upgma / upgma_modified: the merges of a file in a workgroup of its own) or one
-// lcsgpu_lcs_triangles_batch (-gt nj: the host builder per file, on the worker threads; FAMSA_HOST_TEST=batch_upgma_host
-// sends the UPGMA files that way as well).
+// lcsgpu_upgma_batch (-gt upgma / upgma_modified) or one lcsgpu_nj_batch (-gt nj): the merges of a file in a workgroup of
+// its own.  FAMSA_HOST_TEST=batch_upgma_host / batch_nj_host send those files' triangles (lcsgpu_lcs_triangles_batch) to the
+// host builders on the worker threads instead, as does a -gt nj file above LCSGPU_NJ_BATCH_MAX_MEMBERS (with the routing
+// limit lifted).
 // Every file's Newick is what guide_tree_newick_gpu gives for it alone: the same guide_tree_newick runs over a view of
 // the file's slice of the chunk.  Files the chunks do not take -- more unique sequences than the routing limit, a
 // sequence beyond 65535 residues, a tree heuristic that applies, -gt chained, -gt sl with an orientation-sensitive
@@ -33,6 +34,7 @@ struct BatchResult {
 struct BatchTotals {
     int files = 0, chunks = 0, in_chunks = 0, one_file = 0, failed = 0;
     int device_upgma = 0; // files of the chunks whose UPGMA merges ran on the device (lcsgpu_upgma_batch)
+    int device_nj = 0;    // ... whose NJ merges did (lcsgpu_nj_batch)
     // load / sort / newick: summed over the worker threads; upload / device: the driving thread's wall time
     double load_s = 0, sort_s = 0, upload_s = 0, device_s = 0, newick_s = 0, one_file_s = 0;
 };

@@ -227,7 +227,7 @@ int main(int argc, char** argv)
             }
             if (verbose)
                 std::cerr << "batch.files=" << list.size() << "\nbatch.chunks=" << totals.chunks << "\nbatch.files_in_chunks=" << totals.in_chunks
-                          << "\nbatch.files_device_upgma=" << totals.device_upgma
+                          << "\nbatch.files_device_upgma=" << totals.device_upgma << "\nbatch.files_device_nj=" << totals.device_nj
                           << "\nbatch.files_one_file_route=" << totals.one_file << "\nbatch.files_failed=" << failed
                           << "\nbatch.group_max=" << batch_group_max() << "\nbatch.pair_budget=" << batch_pair_budget()
                           << "\ntime.load=" << totals.load_s << "\ntime.sort=" << totals.sort_s << "\ntime.gpu_upload=" << totals.upload_s

@@ -320,6 +320,18 @@ void GpuLcsSource::upgma_nodes_batch(const int* ids, const int64_t* offsets, int
     add_kernel_ms(ctx_);
 }
 
+void GpuLcsSource::nj_nodes_batch(const int* ids, const int64_t* offsets, int n_groups, int distance_kind, std::vector<int32_t>& left,
+                                  std::vector<int32_t>& right, std::vector<int32_t>& status)
+{
+    size_t count = 0;
+    for (int g = 0; g < n_groups; ++g) count += offsets[g + 1] - offsets[g] > 1 ? (size_t)(offsets[g + 1] - offsets[g] - 1) : 0;
+    left.resize(count);
+    right.resize(count);
+    status.assign((size_t)std::max(n_groups, 1), 0);
+    check(lcsgpu_nj_batch(ctx_, ids, offsets, n_groups, distance_kind, left.data(), right.data(), status.data()), "lcsgpu_nj_batch");
+    add_kernel_ms(ctx_);
+}
+
 bool GpuLcsSource::upgma_nodes(int distance_kind, bool modified, std::vector<int32_t>& left, std::vector<int32_t>& right)
 {
     const int m = n() > 0 ? n() - 1 : 0;

@@ -27,7 +27,7 @@ namespace famsa_host {
 // before the second session of round 6: measurements), batch_pairs=N / batch_group_max=N (batch mode: the pair budget of a chunk and
 // the routing limit, batch.h -- tests force several chunks / the one-file route with them; unset, the defaults hold), batch_upgma_host
 // (batch mode: the merges of -gt upgma / upgma_modified files in the host builders over the chunk's triangles, as before
-// lcsgpu_upgma_batch: tests, measurements).  Not read on any product default path beyond that.
+// lcsgpu_upgma_batch: tests, measurements), batch_nj_host (the same for -gt nj files and lcsgpu_nj_batch), matrix_whole_input (MatrixLcsSource below).  Not read on any product default path beyond that.
 bool host_test(const char* name);
 int host_test_int(const char* key, int dflt);
 // LCSGPU_PROFILE: stage / call statistics on stderr (the library prints its own under the same switch)
@@ -149,6 +149,10 @@ public:
     // no finite nearest neighbour and its records are unspecified
     void upgma_nodes_batch(const int* ids, const int64_t* offsets, int n_groups, int distance_kind, bool modified,
                            std::vector<int32_t>& left, std::vector<int32_t>& right, std::vector<int32_t>& status);
+    // the same for neighbour joining (lcsgpu_nj_batch; lists of at most LCSGPU_NJ_BATCH_MAX_MEMBERS members): status[g] = 1: at
+    // some merge no q was below FLT_MAX
+    void nj_nodes_batch(const int* ids, const int64_t* offsets, int n_groups, int distance_kind, std::vector<int32_t>& left,
+                        std::vector<int32_t>& right, std::vector<int32_t>& status);
     // per uploaded sequence: 1 if it is orientation sensitive as a ref (lcsgpu_orientation_flags)
     const std::vector<uint8_t>& orientation_flags() const { return flags_; }
     bool upgma_nodes(int distance_kind, bool modified, std::vector<int32_t>& left, std::vector<int32_t>& right) override;
@@ -204,6 +208,9 @@ public:
     uint32_t length(int i) const override { return lens_[i]; }
     bool orientation_sensitive() const override { return sensitive_; }
     bool wide() const override { return wide_; }
+    // FAMSA_HOST_TEST=matrix_whole_input: the matrix stands for a whole input, as a batch chunk's slice of a file does -- the
+    // host builders then refuse degenerate sets in the device reducers' words, which the CPU tests pin
+    bool whole_input() const override { return host_test("matrix_whole_input"); }
     void triangle(int r0, int r1, LcsBuf& out) override;
     void rect(const int* refs, int n_refs, const int* cols, int n_cols, LcsBuf& out) override;
     // served from the matrix, so the batched-leaf path of the FastTree recursion runs without a GPU too

@@ -72,6 +72,7 @@ def load_library():
         "lcsgpu_upgma": (C.c_int, [vp, C.c_int, C.c_int, vp, vp]),
         "lcsgpu_nj": (C.c_int, [vp, C.c_int, vp, vp]),
         "lcsgpu_upgma_batch": (C.c_int, [vp, pi32, C.POINTER(C.c_int64), i32, C.c_int, C.c_int, vp, vp, vp]),
+        "lcsgpu_nj_batch": (C.c_int, [vp, pi32, C.POINTER(C.c_int64), i32, C.c_int, vp, vp, vp]),
         "lcsgpu_lcs_triangles_batch": (C.c_int, [vp, pi32, C.POINTER(C.c_int64), i32, vp, C.c_int]),
         "lcsgpu_assign_seeds": (C.c_int, [vp, pi32, i32, pi32, i32, C.c_int, i32, vp, vp]),
         "lcsgpu_clarans": (C.c_int, [vp, pi32, i32, C.c_int, i32, i32, C.c_float, i32, pi32]),
@@ -101,6 +102,7 @@ MST_KEY = np.dtype([("dist_bits", np.uint64), ("id", np.uint64)])               
 MST_TRIANGLE_ORIENTATION = 0x100
 MST_BATCH_MAX_MEMBERS = 4096  # lcsgpu_mst_prim_batch: members of one group at most
 UPGMA_BATCH_MAX_MEMBERS = 4096  # lcsgpu_upgma_batch: members of one group at most
+NJ_BATCH_MAX_MEMBERS = 2048  # lcsgpu_nj_batch: members of one group at most
 MST_COMPUTE = 0x200  # lcsgpu_mst_shard_begin: the LCS launch itself does the local half (see include/lcsgpu.h)
 
 
@@ -335,6 +337,17 @@ class LcsGpu:
         (left, right) array pairs, the int32 status array: 0 = built, 1 = no finite nearest neighbour -- that list's
         records are unspecified).  out (optional): the flat int32 arrays (left, right, status) the library writes into, sum
         of max(m - 1, 0) records resp. len(groups) entries at least -- what is returned are then views of them."""
+        return self._node_records_batch(groups, out, lambda ids, offs, n, left, right, status: self._lib.lcsgpu_upgma_batch(
+            self._ctx, ids, offs, n, int(kind), int(bool(modified)), left, right, status))
+
+    def nj_batch(self, groups, kind=1, out=None):
+        """Neighbour-joining trees of several id lists of the uploaded set, one call (lcsgpu_nj_batch): per list what nj
+        returns for that list uploaded alone in list order.  Lists of at most NJ_BATCH_MAX_MEMBERS members.  Returns and
+        `out` as for upgma_batch; status 1 = at some merge no q was below FLT_MAX (nj raises for such a set)."""
+        return self._node_records_batch(groups, out, lambda ids, offs, n, left, right, status: self._lib.lcsgpu_nj_batch(
+            self._ctx, ids, offs, n, int(kind), left, right, status))
+
+    def _node_records_batch(self, groups, out, call):
         sizes = [len(g) for g in groups]
         offs = np.zeros(len(groups) + 1, dtype=np.int64)
         np.cumsum(sizes, out=offs[1:])
@@ -348,9 +361,8 @@ class LcsGpu:
         left, right, status = out
         for arr, need in ((left, int(base[-1])), (right, int(base[-1])), (status, len(groups))):
             assert arr.dtype == np.int32 and arr.flags.c_contiguous and len(arr) >= need
-        self._check(self._lib.lcsgpu_upgma_batch(self._ctx, ids.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                 offs.ctypes.data_as(C.POINTER(C.c_int64)), len(groups), int(kind),
-                                                 int(bool(modified)), left.ctypes.data, right.ctypes.data, status.ctypes.data))
+        self._check(call(ids.ctypes.data_as(C.POINTER(C.c_int32)), offs.ctypes.data_as(C.POINTER(C.c_int64)), len(groups),
+                         left.ctypes.data, right.ctypes.data, status.ctypes.data))
         return ([(left[base[g]:base[g + 1]], right[base[g]:base[g + 1]]) for g in range(len(groups))],
                 status[:len(groups)])
 

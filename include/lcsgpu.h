@@ -400,6 +400,29 @@ int lcsgpu_mst_prim_batch(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* gr
 int lcsgpu_upgma_batch(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* group_offsets, int32_t n_groups,
                        int distance_kind, int modified, int32_t* out_left, int32_t* out_right, int32_t* out_status);
 
+/* Neighbour joining of several id lists in one call; lists, record offsets and node numbers as for
+ * lcsgpu_upgma_batch: exactly what lcsgpu_nj returns for list g uploaded alone in list order.  The lists'
+ * triangles are computed as by lcsgpu_lcs_triangles_batch (ref = the LATER member -- calculateDistanceMatrix's
+ * orientation, so orientation-sensitive sequences are served like any other) and stay on the device; per
+ * slice of lists (at most LCSGPU_TUNE nj_group_mb MB of float triangles, 2048 by default, one list at least)
+ * one launch turns them into packed float triangles (Transform<float, kind>: float pow table, IEEE float
+ * division, lcs == 0: FLT_MAX) with every row's sum in ascending index, and a workgroup per list runs
+ * NeighborJoining::computeTree operation for operation in float: q = (live - 2) D - sum_i - sum_j, the first
+ * strict minimum below FLT_MAX over i < j in the order of the live rows (a NaN never wins), the reference's
+ * row update and its sequential sums.  256 threads per list below 200 members, 1024 from there on
+ * (LCSGPU_TUNE nj_group_threads=256|1024 forces one).
+ * out_status (HOST, n_groups entries): 0 = built (also for lists of fewer than two members); 1 = at some merge
+ * no q was below FLT_MAX (the reference's result is degenerate there; lcsgpu_nj answers LCSGPU_E_INVALID) --
+ * that list's records are unspecified, the others are not affected and the call still returns LCSGPU_OK.
+ * LCSGPU_E_UNSUPPORTED (nothing computed, the outputs untouched): a list of more than
+ * LCSGPU_NJ_BATCH_MAX_MEMBERS members (a list costs m^3 / 6 evaluations of q on ONE compute unit: beyond the
+ * cap lcsgpu_nj's whole-chip launch is the tool); a named sequence longer than 65535 residues.
+ * LCSGPU_E_NOMEM when the device cannot hold one slice.
+ * Replaces: NeighborJoining::run (tree/NeighborJoining.cpp:10-118), once per list. */
+#define LCSGPU_NJ_BATCH_MAX_MEMBERS 2048
+int lcsgpu_nj_batch(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* group_offsets, int32_t n_groups,
+                    int distance_kind, int32_t* out_left, int32_t* out_right, int32_t* out_status);
+
 /* Seed assignment of one FastTree evaluation: for r = 0 .. n_seeds-1 in order,
  *   d = Transform<float>(LCS(ref = seed_ids[r], partner = col_ids[j]));  if (d < dist[j]) { dist[j] = d; assign[j] = first_k + r; }
  * dist / assign (HOST, n_cols entries each) are read and updated: the caller initialises them with the

@@ -22,8 +22,15 @@ square.  (One group alone is the kernel's worst case: what it is for is many gro
 And the same for lcsgpu_upgma_batch: wall time, kernels, the UPGMA launch pair alone (kernels minus those of
 lcsgpu_lcs_triangles_batch: the squares with the rows' initial keys, and the merges) and that per merge step.
 
---gts / --skip-ab / --skip-mst-kernels / --cli narrow a run to some generators, to the batch legs, and to another build's
-famsa-gpu (a comparison with an earlier commit on the same machine).
+And for lcsgpu_nj_batch (--nj-kernel-sizes, --skip-nj-kernels), once per thread count (LCSGPU_TUNE nj_group_threads=256 and
+=1024, a child each): the NJ launches alone (kernels minus those of lcsgpu_lcs_triangles_batch: the float triangles with the
+rows' sums, and the merges), whole and per merge, for one group and for many side by side -- where the two thread counts
+cross is NJ_GROUP_WIDE_AT of csrc/fasttree_kernels.h.
+
+--gts (sl, slink, upgma, upgma_modified, nj) / --sizes / --skip-ab / --skip-mst-kernels / --cli narrow a run to some
+generators, some family sizes, to the batch legs, and to another build's famsa-gpu.  --parent-cli adds a leg (p): that
+build's famsa-gpu -batch (an earlier commit's, on the same machine) timed run by run in alternation with (c), with the
+spread (min .. max) of both.
 
 Writes everything to stdout and to --out (default profiles/batch_trees.txt)."""
 import argparse
@@ -138,6 +145,35 @@ def upgma_child(sizes, reps):
     eng.close()
 
 
+def nj_child(sizes, reps):
+    """Runs in a child per LCSGPU_TUNE nj_group_threads setting: one JSON line per group size for lcsgpu_nj_batch."""
+    import famsa_amd
+    rng = np.random.Generator(np.random.PCG64(77))
+    eng = famsa_amd.LcsGpu(0)
+    for m in sizes:
+        seqs = family(rng, m)
+        eng.upload_seqs(seqs)
+        group = [np.arange(m, dtype=np.int32)]
+        many = max(1, min(256, 65536 // m))
+        groups = group * many
+        rec = {"m": m, "many": many}
+        for name, call in (("nj", lambda: eng.nj_batch(group, 1)), ("triangles", lambda: eng.lcs_triangles_batch(group)),
+                           ("many", lambda: eng.nj_batch(groups, 1)), ("many_triangles", lambda: eng.lcs_triangles_batch(groups))):
+            res = call()
+            if name in ("nj", "many"):
+                assert not res[1].any(), "a family without a tree"
+            wall, ms = [], []
+            for _ in range(reps):
+                t0 = time.perf_counter()
+                call()
+                wall.append(time.perf_counter() - t0)
+                ms.append(eng.last_kernel_ms()[0])
+            rec[name + "_wall_ms"] = 1e3 * statistics.median(wall)
+            rec[name + "_kernel_ms"] = statistics.median(ms)
+        print(json.dumps(rec), flush=True)
+    eng.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batch_trees.txt"))
@@ -148,13 +184,18 @@ def main():
     ap.add_argument("--kernel-sizes", default="50,200,256,500,1000,1500,2000,3000,4096")
     ap.add_argument("--skip-e2e", action="store_true")
     ap.add_argument("--upgma-kernel-sizes", default="50,200,256,500,1000,2000,4096")
-    ap.add_argument("--gts", default="sl,upgma", help="the generators of the files-per-second table")
+    ap.add_argument("--nj-kernel-sizes", default="50,200,256,500,1000,2048")
+    ap.add_argument("--skip-nj-kernels", action="store_true", help="no lcsgpu_nj_batch kernel table (a build without the call)")
+    ap.add_argument("--gts", default="sl,upgma", help="the generators of the files-per-second table (sl, slink, upgma, upgma_modified, nj)")
+    ap.add_argument("--sizes", default=",".join(str(m) for m in SIZES), help="the family sizes of the files-per-second table")
+    ap.add_argument("--parent-cli", default=None, help="an earlier build's famsa-gpu: leg (p), timed in alternation with (c); with --skip-ab that pair is the whole table")
     ap.add_argument("--skip-ab", action="store_true", help="no (a) / (b) legs: the batch legs only")
     ap.add_argument("--skip-mst-kernels", action="store_true", help="no lcsgpu_mst_prim_batch kernel table")
     ap.add_argument("--skip-upgma-kernels", action="store_true", help="no lcsgpu_upgma_batch kernel table (a build without the call)")
     ap.add_argument("--cli", default=None, help="another build's famsa-gpu for the batch legs")
     ap.add_argument("--kernel-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--upgma-child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--nj-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     ksizes = [int(x) for x in args.kernel_sizes.split(",") if x]
     if args.kernel_child:
@@ -162,6 +203,9 @@ def main():
         return
     if args.upgma_child:
         upgma_child([int(x) for x in args.upgma_kernel_sizes.split(",") if x], args.reps)
+        return
+    if args.nj_child:
+        nj_child([int(x) for x in args.nj_kernel_sizes.split(",") if x], args.reps)
         return
 
     lines = []
@@ -211,6 +255,27 @@ def main():
                 r["m"], r["upgma_wall_ms"], r["upgma_kernel_ms"], one, 1e3 * one / max(r["m"] - 1, 1), r["many_wall_ms"] / r["many"],
                 r["many"], many, 1e3 * many / max(r["m"] - 1, 1)))
         say()
+    if not args.skip_nj_kernels:
+        say("## lcsgpu_nj_batch: one group of m members, and many groups of m in one call; nj = kernels - lcsgpu_lcs_triangles_batch")
+        say("## kernels on the same groups (the float triangles with the rows' sums + the merges); per merge = nj / (m - 2);")
+        say("## many: nj/group = nj / groups -- throughput with the groups side by side on the compute units, not a group's own time")
+        for threads in (256, 1024):
+            say("# LCSGPU_TUNE=nj_group_threads=%d" % threads)
+            say("%6s %12s %12s %12s %12s %20s %18s" % ("m", "wall", "kernels", "nj", "per merge", "many: wall", "many: nj/group"))
+            env = dict(os.environ)
+            env["LCSGPU_TUNE"] = "nj_group_threads=%d" % threads
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--nj-child", "--reps", str(args.reps), "--nj-kernel-sizes",
+                                args.nj_kernel_sizes], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
+            if p.returncode != 0:
+                say("FAILED: " + p.stderr[-1500:])
+                return 1
+            for l in p.stdout.splitlines():
+                r = json.loads(l)
+                one = r["nj_kernel_ms"] - r["triangles_kernel_ms"]
+                many = (r["many_kernel_ms"] - r["many_triangles_kernel_ms"]) / r["many"]
+                say("%6d %9.3f ms %9.3f ms %9.3f ms %9.2f us %13.3f ms x%-4d %15.4f ms" % (
+                    r["m"], r["nj_wall_ms"], r["nj_kernel_ms"], one, 1e3 * one / max(r["m"] - 2, 1), r["many_wall_ms"], r["many"], many))
+            say()
     if args.skip_e2e:
         return 0
 
@@ -221,7 +286,12 @@ def main():
     rng = np.random.Generator(np.random.PCG64(2024))
     with tempfile.TemporaryDirectory() as tmp:
         files = {}
+        sizes = [int(x) for x in args.sizes.split(",") if x]
+        if not sizes or any(m not in SIZES for m in sizes):
+            ap.error("--sizes takes some of %s" % ",".join(str(m) for m in SIZES))
         for m, count in zip(SIZES, COUNTS):
+            if m not in sizes:
+                continue
             count = max(1, int(round(count * args.scale)))
             files[m] = []
             for k in range(count):
@@ -237,12 +307,14 @@ def main():
         say("## files per second; (a) one famsa-gpu process per file (first %d files), (b) famsa_amd.guide_tree in a loop in one" % args.files_a)
         say("## process (first %d files), (c) famsa-gpu -batch (all files of the size)" % args.files_b)
         say("## (c1) = (c) with every file sent down the one-file route on the batch's one engine context; (c4096) = (c) with the routing")
-        say("## limit at the kernel's cap: the chunks take every size; (ch) = (c) with the UPGMA merges in the host builders")
+        say("## limit at the kernel's cap: the chunks take every size; (ch) = (c) with the UPGMA / NJ merges in the host builders")
+        if args.parent_cli:
+            say("## (p) = %s -batch, run by run in alternation with (c): medians, and [min .. max] of the timed runs" % args.parent_cli)
         say("%6s %6s %8s %12s %12s %12s %12s %14s %12s %8s %8s" % ("gt", "m", "files", "(a) files/s", "(b) files/s", "(c) files/s", "(c1) files/s",
                                                                "(c4096) files/s", "(ch) files/s", "c / a", "c / b"))
         nan = float("nan")
         for gt in [g for g in args.gts.split(",") if g]:
-            for m in SIZES:
+            for m in sizes:
                 fa, fb, fc = files[m][: args.files_a], files[m][: args.files_b], files[m]
 
                 def run_a():
@@ -258,20 +330,38 @@ def main():
                     for src, dst in zip(fc, outs(fc)):
                         f.write("%s\t%s\n" % (src, dst))
 
-                def run_c(hook=None):
+                def run_c(hook=None, cli=None):
                     env = dict(os.environ)
                     env.pop("FAMSA_HOST_TEST", None)
                     if hook:
                         env["FAMSA_HOST_TEST"] = hook
-                    subprocess.run([CLI, "-gt", gt, "-gt_export", "-batch", lst], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL,
-                                   env=env)
+                    subprocess.run([cli or CLI, "-gt", gt, "-gt_export", "-batch", lst], check=True, stdout=subprocess.DEVNULL,
+                                   stderr=subprocess.DEVNULL, env=env)
 
                 a = nan if args.skip_ab else len(fa) / median_of(run_a, args.reps)
                 b = nan if args.skip_ab else len(fb) / median_of(run_b, args.reps)
+                if args.parent_cli:  # this build and the earlier one, run by run in turn, after a warm-up of each
+                    run_c()
+                    run_c(cli=args.parent_cli)
+                    tc, tp = [], []
+                    for _ in range(args.reps):
+                        for cli, times in ((None, tc), (args.parent_cli, tp)):
+                            t0 = time.perf_counter()
+                            run_c(cli=cli)
+                            times.append(time.perf_counter() - t0)
+                    say("%6s %6d %8d (c) %.1f files/s [%.1f .. %.1f]   (p) %.1f files/s [%.1f .. %.1f]   c / p %.2f" % (
+                        gt, m, len(fc), len(fc) / statistics.median(tc), len(fc) / max(tc), len(fc) / min(tc),
+                        len(fc) / statistics.median(tp), len(fc) / max(tp), len(fc) / min(tp), statistics.median(tp) / statistics.median(tc)))
+                    parent_out = [open(p, "rb").read() for p in outs(fc)]  # (the earlier build ran last)
+                    run_c()
+                    assert parent_out == [open(p, "rb").read() for p in outs(fc)], (gt, m, "this build's bytes differ from the earlier build's")
+                    if args.skip_ab:
+                        continue
                 c = len(fc) / median_of(run_c, args.reps)
                 c1 = len(fc) / median_of(lambda: run_c("batch_group_max=1"), args.reps)
                 c4096 = len(fc) / median_of(lambda: run_c("batch_group_max=4096"), args.reps)
-                ch = len(fc) / median_of(lambda: run_c("batch_upgma_host"), args.reps) if gt.startswith("upgma") else nan
+                ch = len(fc) / median_of(lambda: run_c("batch_upgma_host"), args.reps) if gt.startswith("upgma") else \
+                    len(fc) / median_of(lambda: run_c("batch_nj_host"), args.reps) if gt == "nj" else nan
                 say("%6s %6d %8d %12.1f %12.1f %12.1f %12.1f %14.1f %12.1f %8.1f %8.1f" % (gt, m, len(fc), a, b, c, c1, c4096, ch, c / a, c / b))
                 # the batch's outputs are the one-file command's (spot check on the files (a) wrote last)
                 run_a()
@@ -281,7 +371,7 @@ def main():
         last_gt = [g for g in args.gts.split(",") if g][-1]
         p = subprocess.run([CLI, "-gt", last_gt, "-gt_export", "-batch", lst, "-v"], stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True)
         say()
-        say("## famsa-gpu -gt %s -gt_export -batch -v on the m = %d list" % (last_gt, SIZES[-1]))
+        say("## famsa-gpu -gt %s -gt_export -batch -v on the m = %d list" % (last_gt, sizes[-1]))
         for l in p.stderr.splitlines():
             say(l)
     return 0

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "text_plan.h"
+
 namespace lcsgpu {
 
 enum { MODE_RECT = 0, MODE_TRIANGLE = 1 };
@@ -316,6 +318,28 @@ struct TextArgs {
     int32_t segs;            // segments (text_segment_values() values each) per row
 };
 hipError_t launch_text_block(const TextArgs& t, hipStream_t stream);
+// The rows of MANY id lists in one launch sequence (lcsgpu_dist_text_batch): the tables are text_plan.h's, the values the
+// lists' 16-bit LCS triangles (lower form: the launches of lcsgpu_lcs_triangles_batch) or m x m rectangles (square form).
+struct TextGroupArgs {
+    const uint16_t* lcs;                  // all lists' triangles or rectangles; TextRow::src counts from here
+    const lcsgpu_impl::TextRow* rows;     // [n_rows + 1]
+    const int32_t* job_row;               // [n_jobs]
+    const int32_t* ids;                   // the call's concatenated id lists
+    const int64_t* list_row0;             // [n_groups + 1]
+    const uint32_t* lens;
+    const double* pow_f64;
+    const char* names;                    // the names of the uploaded set without '>' ...
+    const uint64_t* name_off;             // ... name i = names[name_off[i] .. name_off[i + 1])
+    uint32_t* seg_len;                    // [n_jobs] bytes of a segment, then its offset inside the row
+    uint32_t* row_len;                    // [n_rows]
+    unsigned long long* row_start;        // [n_rows + 1]
+    unsigned long long* list_start;       // [n_groups + 1] where a list's rows start in the call's text; [n_groups] = its bytes
+    char* out;                            // the call's text (the write pass only)
+    int32_t kind;                         // as TextArgs::kind
+    int32_t n_rows, n_jobs, n_groups;
+};
+hipError_t launch_text_group_lengths(const TextGroupArgs& g, hipStream_t stream); // 4 launches
+hipError_t launch_text_group_write(const TextGroupArgs& g, hipStream_t stream);   // 1 launch
 int text_segment_values();
 int text_max_value_bytes();
 

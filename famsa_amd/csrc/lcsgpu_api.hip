@@ -563,6 +563,8 @@ int lcsgpu_destroy(lcsgpu_ctx* ctx)
     ctx->d_qrows.release();
     ctx->d_qcols.release();
     ctx->d_dist.release();
+    ctx->d_batch_text.release();
+    for (PinBuf& b : ctx->h_batch_text) b.release();
     delete ctx;
     return LCSGPU_OK;
 }

@@ -109,9 +109,12 @@ static int launch_job_tables(lcsgpu_ctx* ctx, Lane& L, const std::vector<JobBuck
 // launches are queued on L.stream (or, with a ref beyond 2048 residues in the batch, already finished).
 // `before_launch` (may be empty) is called once the plan is made, before the first thing goes to the device: the caller's moment
 // to take the compute gate (planning a few hundred lists is tens of milliseconds of host work nobody should wait for).
+// square (lcsgpu_dist_text_batch's square form): instead of its triangle every list gets its whole m x m rectangle, row k =
+// LCS(ref = member k, partner = every member, itself included), in the kernels' rectangle mode as lcsgpu_assign_seeds_batch
+// runs it -- every member is a ref, so the upper half and the diagonal are computed in their own orientation, not mirrored.
 static int batch_triangles_to_device(lcsgpu_ctx* ctx, Lane& L, const int32_t* ids, const int64_t* group_offsets, int32_t n_groups,
                                      int elem_size, std::vector<int64_t>& tri_base, int64_t* count_out, bool* had_long,
-                                     const std::function<void()>& before_launch = nullptr)
+                                     const std::function<void()>& before_launch = nullptr, bool square = false)
 {
     if (!ctx) return fail(LCSGPU_E_INVALID, "NULL ctx");
     if (ctx->n < 0) return fail(LCSGPU_E_STATE, "no sequence set uploaded");
@@ -130,7 +133,7 @@ static int batch_triangles_to_device(lcsgpu_ctx* ctx, Lane& L, const int32_t* id
     for (int32_t g = 0; g < n_groups; ++g) {
         const int64_t m = group_offsets[g + 1] - group_offsets[g];
         if (m < 0) return fail(LCSGPU_E_INVALID, "group_offsets not ascending");
-        tri_base[g + 1] = tri_base[g] + m * (m - 1) / 2;
+        tri_base[g + 1] = tri_base[g] + (square ? m * m : m * (m - 1) / 2);
     }
     const int64_t count = tri_base[n_groups];
     if (count <= 0) return LCSGPU_OK;
@@ -160,10 +163,11 @@ static int batch_triangles_to_device(lcsgpu_ctx* ctx, Lane& L, const int32_t* id
         int launches = 0;
         for (int32_t g = 0; g < n_groups; ++g) {
             const int32_t m = (int32_t)(group_offsets[g + 1] - group_offsets[g]);
-            if (m < 2) continue;
+            if (m < (square ? 1 : 2)) continue;
             const int32_t* gi = ids + group_offsets[g];
-            int rc = run_rows(ctx, L, lcsgpu::MODE_TRIANGLE, gi, 0, m, gi, 0, m - 1,
-                              (char*)L.d_out.p + (size_t)tri_base[g] * elem_size, 0, 0, elem_size);
+            char* const to = (char*)L.d_out.p + (size_t)tri_base[g] * elem_size;
+            int rc = square ? run_rows(ctx, L, lcsgpu::MODE_RECT, gi, 0, m, gi, 0, m, to, m, 0, elem_size)
+                            : run_rows(ctx, L, lcsgpu::MODE_TRIANGLE, gi, 0, m, gi, 0, m - 1, to, 0, 0, elem_size);
             if (rc) return rc;
             HIP_TRY(hipStreamSynchronize(L.stream));
             finish_host_call(ctx, L);
@@ -176,7 +180,7 @@ static int batch_triangles_to_device(lcsgpu_ctx* ctx, Lane& L, const int32_t* id
     }
 
     // the refs: every member but a list's first, which has no partner; rows and columns are positions in `ids`, a ref's
-    // columns end at its own row
+    // columns end at its own row (square: every member, its columns the whole list, its row of the rectangle its own)
     static const int narrow_max = tune_int("narrow_lists", 192); // lists up to that many members run in one-wave workgroups
     double inv_refs[65];
     for (int h = 0; h <= 64; ++h) inv_refs[h] = 1.0 / lcsgpu::refs_per_block_for(h, false, 1, 1);
@@ -184,10 +188,11 @@ static int batch_triangles_to_device(lcsgpu_ctx* ctx, Lane& L, const int32_t* id
     refs.reserve((size_t)n_total);
     for (int32_t g = 0; g < n_groups; ++g) {
         const int64_t g0 = group_offsets[g], g1 = group_offsets[g + 1];
-        for (int64_t p = g0 + 1; p < g1; ++p) {
+        for (int64_t p = square ? g0 : g0 + 1; p < g1; ++p) {
             const uint8_t c = cls[(size_t)p];
             const bool q = (c & 0x80) != 0;
-            refs.push_back(JobRef{ids[p], g, (int32_t)g0, p, tri_base[g], q ? 0.0 : (double)((p - g0 + 255) / 256) * inv_refs[c], c,
+            const int64_t col_end = square ? g1 : p, out0 = square ? tri_base[g] + (p - g0) * (g1 - g0) : tri_base[g];
+            refs.push_back(JobRef{ids[p], g, (int32_t)g0, col_end, out0, q ? 0.0 : (double)((col_end - g0 + 255) / 256) * inv_refs[c], c,
                                   (uint8_t)(q ? lcsgpu::quirk_h_class(ctx->lens[ids[p]]) : 0), !q && g1 - g0 <= narrow_max});
         }
     }
@@ -203,7 +208,8 @@ static int batch_triangles_to_device(lcsgpu_ctx* ctx, Lane& L, const int32_t* id
                 plan_calls.load(), 1e-3 * plan_us[0] / plan_calls, 1e-3 * plan_us[1] / plan_calls, 1e-3 * plan_us[2] / plan_calls, 1e-3 * plan_us[3] / plan_calls,
                 (long long)n_total, n_groups);
     if (before_launch) before_launch();
-    return launch_job_tables(ctx, L, buckets, lay, lcsgpu::MODE_TRIANGLE, (const int32_t*)L.d_plan.p /* its first table */, n_total, elem_size);
+    return launch_job_tables(ctx, L, buckets, lay, square ? lcsgpu::MODE_RECT : lcsgpu::MODE_TRIANGLE,
+                             (const int32_t*)L.d_plan.p /* its first table */, n_total, elem_size);
 }
 
 static int lcs_triangles_batch_impl(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* group_offsets, int32_t n_groups, void* out,
@@ -630,6 +636,125 @@ static int nj_batch_impl(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* gro
         memcpy(out_left, back.data(), (size_t)n_nodes * 4);
         memcpy(out_right, back.data() + (o_right - o_left), (size_t)n_nodes * 4);
         memcpy(out_status, back.data() + (o_status - o_left), (size_t)n_groups * 4);
+        return LCSGPU_OK;
+    });
+}
+
+// -dist_export for many id lists in one call: the lists' triangles (lower form; the launches of lcsgpu_lcs_triangles_batch) or
+// m x m rectangles (square form) stay in the lane's result buffer, the job-table form of the formatter (text_kernels.hip,
+// tables from text_plan.h) turns all rows of all lists into text: lengths and scans, the lists' offsets and the total to the
+// host -- the call's one synchronisation in the middle --, the exactly sized output, the write pass, one copy back.
+static int dist_text_batch_impl(lcsgpu_ctx* ctx, const char* names, const uint64_t* name_offsets, const int32_t* ids,
+                                const int64_t* group_offsets, int32_t n_groups, int distance_kind, int flags, const char** text,
+                                uint64_t* text_offsets)
+{
+    const bool pid = (flags & LCSGPU_TEXT_PID) != 0, square = (flags & LCSGPU_TEXT_SQUARE) != 0;
+    // everything that refuses comes first: nothing is computed, the outputs stay as they are
+    if (!ctx) return fail(LCSGPU_E_INVALID, "NULL ctx");
+    if (!name_offsets || !text || !text_offsets) return fail(LCSGPU_E_INVALID, "NULL argument");
+    int rc = check_groups(
+        ctx, ids, group_offsets, n_groups, pid ? LCSGPU_DIST_INDEL075_DIV_LCS : distance_kind,
+        [&](int32_t g, int64_t m) {
+            if (m > LCSGPU_DIST_TEXT_BATCH_MAX_MEMBERS)
+                return fail(LCSGPU_E_UNSUPPORTED, "group %d has %lld members: the batched text handles at most %d (use lcsgpu_dist_text_begin)", g,
+                            (long long)m, LCSGPU_DIST_TEXT_BATCH_MAX_MEMBERS);
+            return 0;
+        },
+        [&](int32_t id) {
+            if (ctx->lens[(size_t)id] > 65535)
+                return fail(LCSGPU_E_UNSUPPORTED, "sequence %d is longer than 65535 residues: the batched text keeps 16-bit LCS values", id);
+            return 0;
+        });
+    if (rc) return rc;
+    const int32_t n = ctx->n;
+    for (int32_t i = 0; i < n; ++i)
+        if (name_offsets[i + 1] < name_offsets[i]) return fail(LCSGPU_E_INVALID, "name offsets not monotone at %d", i);
+    const uint64_t name_base = n > 0 ? name_offsets[0] : 0, name_bytes = n > 0 ? name_offsets[n] - name_base : 0;
+    if (name_bytes > 0 && !names) return fail(LCSGPU_E_INVALID, "NULL names");
+    lcsgpu_impl::TextPlan plan;
+    if (!plan_text(group_offsets, n_groups, square, plan)) return fail(LCSGPU_E_INVALID, "batch too large");
+    const int64_t n_rows = (int64_t)plan.rows.size() - 1, n_jobs = (int64_t)plan.job_row.size(), n_total = n_rows;
+
+    HIP_TRY(hipSetDevice(ctx->device));
+    PinBuf& h_text = ctx->h_batch_text[ctx->batch_text_next]; // the buffer of the call before the last one: its text ends here
+    if (n_rows == 0) { // no list, or empty lists only
+        if (h_text.reserve(16) != hipSuccess) return fail(LCSGPU_E_NOMEM, "the batched text: no pinned host memory");
+        ctx->batch_text_next ^= 1;
+        *text = (const char*)h_text.p;
+        std::fill(text_offsets, text_offsets + n_groups + 1, (uint64_t)0);
+        return LCSGPU_OK;
+    }
+    std::vector<uint64_t> name_off(name_offsets, name_offsets + n + 1);
+    for (uint64_t& o : name_off) o -= name_base;
+
+    GroupCall call(ctx);
+    Lane& L = call.L;
+    // (not GroupCall::triangles: a call whose lists hold no pair still has its "name\n" rows to make)
+    rc = batch_triangles_to_device(ctx, L, ids, group_offsets, n_groups, 2, call.tri_base, &call.count, &call.had_long, [&] { call.hold.lock(); }, square);
+    if (rc) return rc;
+    if (call.count <= 0) { // nothing was launched: the text kernels are the call's own
+        call.hold.lock();
+        L.last_launches = 0;
+        HIP_TRY(hipEventRecord(L.ev_start, L.stream));
+        L.timing_valid = true;
+    } else if (call.tri_base != plan.list_src0)
+        return fail(LCSGPU_E_STATE, "the batched text's plan and its LCS launches disagree about the lists' places");
+    const size_t o_rows = 0, o_job = o_rows + a256(plan.rows.size() * sizeof(lcsgpu_impl::TextRow)), o_ids = o_job + a256((size_t)n_jobs * 4),
+                 o_lrow = o_ids + a256((size_t)n_total * 4), o_names = o_lrow + a256(((size_t)n_groups + 1) * 8),
+                 o_noff = o_names + a256((size_t)name_bytes + 16), o_seg = o_noff + a256(((size_t)n + 1) * 8),
+                 o_rlen = o_seg + a256((size_t)n_jobs * 4), o_rstart = o_rlen + a256((size_t)n_rows * 4),
+                 o_lstart = o_rstart + a256(((size_t)n_rows + 1) * 8), total = o_lstart + a256(((size_t)n_groups + 1) * 8);
+    rc = reserve_big(ctx, L.d_work, total, "the batched text's tables");
+    if (rc) return rc;
+    HIP_TRY(L.h_small.reserve(((size_t)n_groups + 1) * 8));
+    char* base = (char*)L.d_work.p;
+    HIP_TRY(hipMemcpyAsync(base + o_rows, plan.rows.data(), plan.rows.size() * sizeof(lcsgpu_impl::TextRow), hipMemcpyHostToDevice, L.stream));
+    HIP_TRY(hipMemcpyAsync(base + o_job, plan.job_row.data(), (size_t)n_jobs * 4, hipMemcpyHostToDevice, L.stream));
+    HIP_TRY(hipMemcpyAsync(base + o_ids, ids, (size_t)n_total * 4, hipMemcpyHostToDevice, L.stream));
+    HIP_TRY(hipMemcpyAsync(base + o_lrow, plan.list_row0.data(), ((size_t)n_groups + 1) * 8, hipMemcpyHostToDevice, L.stream));
+    if (name_bytes) HIP_TRY(hipMemcpyAsync(base + o_names, names + name_base, (size_t)name_bytes, hipMemcpyHostToDevice, L.stream));
+    HIP_TRY(hipMemcpyAsync(base + o_noff, name_off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, L.stream));
+    lcsgpu::TextGroupArgs g{};
+    g.lcs = (const uint16_t*)L.d_out.p;
+    g.rows = (const lcsgpu_impl::TextRow*)(base + o_rows);
+    g.job_row = (const int32_t*)(base + o_job);
+    g.ids = (const int32_t*)(base + o_ids);
+    g.list_row0 = (const int64_t*)(base + o_lrow);
+    g.lens = (const uint32_t*)ctx->d_lens.p;
+    g.pow_f64 = (const double*)ctx->d_pow.p;
+    g.names = (const char*)(base + o_names);
+    g.name_off = (const uint64_t*)(base + o_noff);
+    g.seg_len = (uint32_t*)(base + o_seg);
+    g.row_len = (uint32_t*)(base + o_rlen);
+    g.row_start = (unsigned long long*)(base + o_rstart);
+    g.list_start = (unsigned long long*)(base + o_lstart);
+    g.kind = pid ? 2 : distance_kind;
+    g.n_rows = (int32_t)n_rows;
+    g.n_jobs = (int32_t)n_jobs;
+    g.n_groups = n_groups;
+    if (const hipError_t e = lcsgpu::launch_text_group_lengths(g, L.stream))
+        return fail(LCSGPU_E_HIP, "the batched text's length launches failed: %s", hipGetErrorString(e));
+    // the lists' offsets and the total: what sizes the output exactly (39 B per value, the worst case, would forbid the
+    // chunks the callers make)
+    HIP_TRY(hipMemcpyAsync(L.h_small.p, g.list_start, ((size_t)n_groups + 1) * 8, hipMemcpyDeviceToHost, L.stream));
+    HIP_TRY(hipEventRecord(L.ev_done, L.stream));
+    HIP_TRY(hipEventSynchronize(L.ev_done));
+    const uint64_t* list_start = (const uint64_t*)L.h_small.p;
+    const uint64_t bytes = list_start[n_groups];
+    rc = reserve_big(ctx, ctx->d_batch_text, (size_t)bytes + 64, "the batched text");
+    if (rc) return rc;
+    if (h_text.reserve((size_t)bytes + 16) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(LCSGPU_E_NOMEM, "the batched text: %llu bytes of pinned host memory", (unsigned long long)bytes);
+    }
+    g.out = (char*)ctx->d_batch_text.p;
+    if (const hipError_t e = lcsgpu::launch_text_group_write(g, L.stream))
+        return fail(LCSGPU_E_HIP, "the batched text's write launch failed: %s", hipGetErrorString(e));
+    return call.finish(5, [&] {
+        HIP_TRY(hipMemcpy(h_text.p, ctx->d_batch_text.p, (size_t)bytes, hipMemcpyDeviceToHost));
+        ctx->batch_text_next ^= 1;
+        *text = (const char*)h_text.p;
+        std::copy(list_start, list_start + n_groups + 1, text_offsets);
         return LCSGPU_OK;
     });
 }
@@ -1194,6 +1319,13 @@ int lcsgpu_nj_batch(lcsgpu_ctx* ctx, const int32_t* ids, const int64_t* group_of
                     int32_t* out_left, int32_t* out_right, int32_t* out_status)
 {
     return guarded("batched NJ", nj_batch_impl, ctx, ids, group_offsets, n_groups, distance_kind, out_left, out_right, out_status);
+}
+
+int lcsgpu_dist_text_batch(lcsgpu_ctx* ctx, const char* names, const uint64_t* name_offsets, const int32_t* ids,
+                           const int64_t* group_offsets, int32_t n_groups, int distance_kind, int flags, const char** text,
+                           uint64_t* text_offsets)
+{
+    return guarded("batched text", dist_text_batch_impl, ctx, names, name_offsets, ids, group_offsets, n_groups, distance_kind, flags, text, text_offsets);
 }
 
 int lcsgpu_assign_seeds(lcsgpu_ctx* ctx, const int32_t* seed_ids, int32_t n_seeds, const int32_t* col_ids,

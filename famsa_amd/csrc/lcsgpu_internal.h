@@ -264,6 +264,11 @@ struct lcsgpu_ctx {
         bool passes_stand = false;
     } mst;
     double total_kernel_ms = 0; // completed host-memory calls
+    // lcsgpu_dist_text_batch: the call's device text, and the two pinned buffers its results alternate between (a call's
+    // text stays valid while the next call runs); kept from call to call, freed by lcsgpu_destroy
+    lcsgpu_impl::DevBuf d_batch_text;
+    lcsgpu_impl::PinBuf h_batch_text[2];
+    int batch_text_next = 0;
 };
 
 namespace lcsgpu_impl {

@@ -1,7 +1,12 @@
 #include "batch.h"
 
+#include <fcntl.h>
+#include <unistd.h>
+
 #include <algorithm>
+#include <cerrno>
 #include <chrono>
+#include <cstring>
 #include <condition_variable>
 #include <deque>
 #include <future>
@@ -27,15 +32,16 @@ struct ChunkPacker {
     int group_max;
     int chunk = -1;
     int64_t used = 0;
-    int place(int64_t m, bool eligible)
+    int place(int64_t m, bool eligible) { return place(m, m > 1 ? m * (m - 1) / 2 : 0, eligible); }
+    // ... with what the file takes of the budget given by the caller (the matrices of -dist_export: their values)
+    int place(int64_t m, int64_t cost, bool eligible)
     {
         if (!eligible || m > group_max) return -1;
-        const int64_t pairs = m > 1 ? m * (m - 1) / 2 : 0;
-        if (chunk < 0 || used + pairs > budget) {
+        if (chunk < 0 || used + cost > budget) {
             ++chunk;
             used = 0;
         }
-        used += pairs;
+        used += cost;
         return chunk;
     }
 };
@@ -184,6 +190,16 @@ int64_t batch_pair_budget()
     return (int64_t)std::max(1, host_test_int("batch_pairs", 1 << 30));
 }
 
+int64_t batch_value_budget()
+{
+    // A value is ~9 B of text that the workers have to put into files, and a chunk's files are written while the NEXT chunk is
+    // computed: chunks of 4 x 10^6 values (~38 MB of text) against one chunk for everything (profiles/batch_dist.txt, files per
+    // second, medians of alternating runs): 430 against 220 at 1000 members, where the writes are most of the time (264
+    // against 192 in an earlier run); 2092 against 2203 and 2629 against 2035 at 200 and 50, both inside each other's
+    // run-to-run range.
+    return std::min<int64_t>(batch_pair_budget(), std::max(1, host_test_int("batch_values", 1 << 22)));
+}
+
 int batch_group_max()
 {
     // The largest measured family size at which the chunks are ahead of both the one-file route on the same context and a
@@ -203,34 +219,30 @@ int batch_plan(const std::vector<int64_t>& unique_counts, const std::vector<uint
     return packer.chunk + 1;
 }
 
-std::vector<BatchResult> guide_trees_newick_gpu(const std::vector<BatchJob>& jobs, int device, BatchTotals* totals, EngineFuture* engine,
-                                                const std::function<void(size_t, const BatchResult&)>& done)
-{
-    const size_t n = jobs.size();
-    std::vector<BatchResult> results(n);
-    BatchTotals tot;
-    tot.files = (int)n;
-    if (n == 0) {
-        if (totals) *totals = tot;
-        return results;
-    }
-    EngineFuture own;
-    if (!engine) {
-        own = start_engine(device); // HIP initialisation runs beside the first loads
-        engine = &own;
-    }
-    int n_threads = jobs[0].opt.fast.n_threads;
-    for (const auto& j : jobs) n_threads = std::min(n_threads, j.opt.fast.n_threads);
-    n_threads = std::max(1, n_threads);
+namespace {
 
-    std::mutex tot_mu; // the totals the workers add to
-    std::vector<std::shared_ptr<Loaded>> loaded(n);
-    std::vector<std::future<void>> load_done(n);
-    auto finish = [&](size_t i, BatchResult&& r) {
+// What the batches share (guide trees, distance matrices): the files' results and totals, failure isolation, the worker pool
+// that loads files ahead of the device, the one engine, and the walk over the files in order -- chunk by chunk, then the
+// one-file route.
+class Driver {
+public:
+    using Done = std::function<void(size_t, const BatchResult&)>;
+    Driver(size_t n_files, int n_threads, int device, EngineFuture* engine, const Done& done)
+        : n(n_files), results(n_files), loaded(n_files), load_done_(n_files), done_(done), engine_(engine), pool(std::max(1, n_threads))
+    {
+        tot.files = (int)n;
+        if (!engine_ && n > 0) {
+            own_ = start_engine(device); // HIP initialisation runs beside the first loads
+            engine_ = &own_;
+        }
+    }
+    void finish(size_t i, BatchResult&& r)
+    {
         results[i] = std::move(r);
-        if (done) done(i, results[i]);
-    };
-    auto fail_file = [&](size_t i, const std::string& why, int route) {
+        if (done_) done_(i, results[i]);
+    }
+    void fail_file(size_t i, const std::string& why, int route)
+    {
         BatchResult r;
         r.message = why;
         r.route = route;
@@ -239,65 +251,148 @@ std::vector<BatchResult> guide_trees_newick_gpu(const std::vector<BatchJob>& job
             ++tot.failed;
         }
         finish(i, std::move(r));
-    };
-
-    auto load_one = [&](size_t i) {
-        auto f = std::make_shared<Loaded>();
-        const TreeOptions& opt = jobs[i].opt;
-        try {
-            const double t0 = now_s();
-            f->s = load_fasta(jobs[i].input, 1);
-            if (f->s.size() == 0) throw std::runtime_error("no sequences in " + jobs[i].input);
-            const double t1 = now_s();
-            f->w = make_workset(f->s, opt.keep_duplicates, 1);
-            f->in_of.resize((size_t)f->w.n_unique());
-            for (int a = 0; a < f->w.n_unique(); ++a) f->in_of[(size_t)a] = f->w.sorted2input[(size_t)f->w.unique2sorted[(size_t)a]];
-            uint32_t longest = 0;
-            for (size_t r = 0; r < f->s.size(); ++r) longest = std::max(longest, f->s.length(r));
-            // what guide_tree_newick decides for the file alone: a heuristic applies from the threshold on (all records count)
-            const bool heuristic = opt.heuristic != 0 && (int)f->s.size() >= opt.fast.threshold;
-            f->eligible = longest <= 65535 && !heuristic && opt.method != GT::chained &&
-                          (opt.dist == Distance::indel_div_lcs || opt.dist == Distance::indel075_div_lcs);
-            f->ok = true;
-            const double t2 = now_s();
-            std::lock_guard<std::mutex> lk(tot_mu);
-            tot.load_s += t1 - t0;
-            tot.sort_s += t2 - t1;
-        } catch (const std::exception& e) {
-            f->message = e.what();
-        }
-        loaded[i] = f;
-    };
-
-    Pool pool(n_threads);
-    size_t submitted = 0;
-    const size_t lookahead = 256; // files loaded ahead of the chunk the device works on
-    auto submit_loads = [&](size_t upto) {
-        for (; submitted < std::min(n, upto); ++submitted) {
-            const size_t i = submitted;
-            auto pr = std::make_shared<std::promise<void>>();
-            load_done[i] = pr->get_future();
-            pool.submit([&load_one, i, pr] {
-                load_one(i);
-                pr->set_value();
-            });
-        }
-    };
-
-    std::unique_ptr<GpuLcsSource> held;
-    std::string engine_error;
-    auto the_engine = [&]() -> GpuLcsSource* {
-        if (!held && engine_error.empty()) {
+    }
+    GpuLcsSource* the_engine()
+    {
+        if (!held_ && engine_error.empty()) {
             try {
-                held = engine->get();
+                held_ = engine_->get();
             } catch (const std::exception& e) {
                 engine_error = e.what();
             }
         }
-        return held.get();
-    };
+        return held_.get();
+    }
+    // load_one(i, f) fills f (on a worker; what it throws is the file's message); place(i) = the file's chunk number or -1;
+    // run_chunk(files) when a chunk is full; then one_file_route(i, engine) for one_file, in list order
+    void run(const std::function<void(size_t, Loaded&)>& load_one, const std::function<int(size_t)>& place,
+             const std::function<void(const std::vector<size_t>&)>& run_chunk, const std::function<void(size_t, GpuLcsSource&)>& one_file_route)
+    {
+        size_t submitted = 0;
+        const size_t lookahead = 256; // files loaded ahead of the chunk the device works on
+        auto submit_loads = [&](size_t upto) {
+            for (; submitted < std::min(n, upto); ++submitted) {
+                const size_t i = submitted;
+                auto pr = std::make_shared<std::promise<void>>();
+                load_done_[i] = pr->get_future();
+                pool.submit([this, &load_one, i, pr] {
+                    auto f = std::make_shared<Loaded>();
+                    try {
+                        load_one(i, *f);
+                        f->ok = true;
+                    } catch (const std::exception& e) {
+                        f->message = e.what();
+                    }
+                    loaded[i] = f;
+                    pr->set_value();
+                });
+            }
+        };
+        std::vector<size_t> current;
+        int current_chunk = -1;
+        for (size_t i = 0; i < n; ++i) {
+            submit_loads(i + lookahead);
+            load_done_[i].get();
+            const Loaded& f = *loaded[i];
+            if (!f.ok) {
+                fail_file(i, f.message, -1);
+                loaded[i].reset();
+                continue;
+            }
+            const int c = place(i);
+            if (c < 0) {
+                one_file.push_back(i);
+                continue;
+            }
+            if (c != current_chunk && !current.empty()) { // the chunk is full: the device takes it while the workers load on
+                run_chunk(current);
+                current.clear();
+            }
+            current_chunk = c;
+            current.push_back(i);
+        }
+        if (!current.empty()) run_chunk(current);
 
-    std::vector<size_t> one_file; // in list order; the chunks add the -gt sl files they find an orientation-sensitive member in
+        // everything else: today's one-file path, one after the other, on the same engine
+        std::sort(one_file.begin(), one_file.end());
+        for (size_t i : one_file) {
+            GpuLcsSource* src = the_engine();
+            if (!src) {
+                fail_file(i, engine_error, 1);
+                continue;
+            }
+            try {
+                one_file_route(i, *src);
+            } catch (const std::exception& e) {
+                fail_file(i, e.what(), 1);
+            }
+            loaded[i].reset();
+        }
+        pool.wait_idle();
+        if (g_abandon_engine_at_return && !profile_on()) (void)held_.release();
+    }
+
+    const size_t n;
+    std::vector<BatchResult> results;
+    BatchTotals tot;
+    std::mutex tot_mu; // the totals the workers add to
+    std::vector<std::shared_ptr<Loaded>> loaded;
+    std::string engine_error;
+    std::vector<size_t> one_file; // in list order; a chunk may add files it cannot serve
+
+private:
+    std::vector<std::future<void>> load_done_;
+    Done done_;
+    EngineFuture own_, *engine_;
+    std::unique_ptr<GpuLcsSource> held_;
+
+public:
+    Pool pool; // (the last member: its threads end before anything they use does)
+};
+
+} // namespace
+
+std::vector<BatchResult> guide_trees_newick_gpu(const std::vector<BatchJob>& jobs, int device, BatchTotals* totals, EngineFuture* engine,
+                                                const std::function<void(size_t, const BatchResult&)>& done)
+{
+    const size_t n = jobs.size();
+    if (n == 0) {
+        BatchTotals none;
+        if (totals) *totals = none;
+        return {};
+    }
+    int n_threads = jobs[0].opt.fast.n_threads;
+    for (const auto& j : jobs) n_threads = std::min(n_threads, j.opt.fast.n_threads);
+    Driver d(n, n_threads, device, engine, done);
+    BatchTotals& tot = d.tot;
+    std::mutex& tot_mu = d.tot_mu;
+    std::vector<std::shared_ptr<Loaded>>& loaded = d.loaded;
+    Pool& pool = d.pool;
+    std::vector<size_t>& one_file = d.one_file; // the chunks add the -gt sl files they find an orientation-sensitive member in
+    auto finish = [&](size_t i, BatchResult&& r) { d.finish(i, std::move(r)); };
+    auto fail_file = [&](size_t i, const std::string& why, int route) { d.fail_file(i, why, route); };
+
+    auto load_one = [&](size_t i, Loaded& ld) {
+        Loaded* f = &ld;
+        const TreeOptions& opt = jobs[i].opt;
+        const double t0 = now_s();
+        f->s = load_fasta(jobs[i].input, 1);
+        if (f->s.size() == 0) throw std::runtime_error("no sequences in " + jobs[i].input);
+        const double t1 = now_s();
+        f->w = make_workset(f->s, opt.keep_duplicates, 1);
+        f->in_of.resize((size_t)f->w.n_unique());
+        for (int a = 0; a < f->w.n_unique(); ++a) f->in_of[(size_t)a] = f->w.sorted2input[(size_t)f->w.unique2sorted[(size_t)a]];
+        uint32_t longest = 0;
+        for (size_t r = 0; r < f->s.size(); ++r) longest = std::max(longest, f->s.length(r));
+        // what guide_tree_newick decides for the file alone: a heuristic applies from the threshold on (all records count)
+        const bool heuristic = opt.heuristic != 0 && (int)f->s.size() >= opt.fast.threshold;
+        f->eligible = longest <= 65535 && !heuristic && opt.method != GT::chained &&
+                      (opt.dist == Distance::indel_div_lcs || opt.dist == Distance::indel075_div_lcs);
+        const double t2 = now_s();
+        std::lock_guard<std::mutex> lk(tot_mu);
+        tot.load_s += t1 - t0;
+        tot.sort_s += t2 - t1;
+    };
 
     // what a chunk's device calls leave behind for the workers
     struct ChunkData {
@@ -306,9 +401,9 @@ std::vector<BatchResult> guide_trees_newick_gpu(const std::vector<BatchJob>& job
         std::vector<int32_t> left[6], right[6], status[6]; // UPGMA by (modified, distance kind), then NJ by distance kind
     };
     auto run_chunk = [&](const std::vector<size_t>& files) {
-        GpuLcsSource* src = the_engine();
+        GpuLcsSource* src = d.the_engine();
         if (!src) {
-            for (size_t i : files) fail_file(i, engine_error, 0);
+            for (size_t i : files) fail_file(i, d.engine_error, 0);
             return;
         }
         std::vector<size_t> pending = files; // not finished yet: what an error of the chunk's calls fails
@@ -454,60 +549,227 @@ std::vector<BatchResult> guide_trees_newick_gpu(const std::vector<BatchJob>& job
     };
 
     ChunkPacker packer{batch_pair_budget(), batch_group_max()};
-    std::vector<size_t> current;
-    int current_chunk = -1;
-    for (size_t i = 0; i < n; ++i) {
-        submit_loads(i + lookahead);
-        load_done[i].get();
-        const Loaded& f = *loaded[i];
-        if (!f.ok) {
-            fail_file(i, f.message, -1);
-            loaded[i].reset();
-            continue;
-        }
-        const int c = packer.place(f.w.n_unique(), f.eligible);
-        if (c < 0) {
-            one_file.push_back(i);
-            continue;
-        }
-        if (c != current_chunk && !current.empty()) { // the chunk is full: the device takes it while the workers load on
-            run_chunk(current);
-            current.clear();
-        }
-        current_chunk = c;
-        current.push_back(i);
-    }
-    if (!current.empty()) run_chunk(current);
+    d.run(load_one, [&](size_t i) { return packer.place(loaded[i]->w.n_unique(), loaded[i]->eligible); }, run_chunk,
+          [&](size_t i, GpuLcsSource& src) {
+              const double t0 = now_s();
+              BatchResult r;
+              r.newick = guide_tree_newick_gpu(loaded[i]->s, src, jobs[i].opt, nullptr);
+              r.ok = true;
+              r.route = 1;
+              {
+                  std::lock_guard<std::mutex> lk(tot_mu);
+                  tot.one_file_s += now_s() - t0;
+                  ++tot.one_file;
+              }
+              finish(i, std::move(r));
+          });
+    if (totals) *totals = tot;
+    return std::move(d.results);
+}
 
-    // everything else: today's one-file path, one after the other, on the same engine
-    std::sort(one_file.begin(), one_file.end());
-    for (size_t i : one_file) {
-        GpuLcsSource* src = the_engine();
+namespace {
+
+// header (may be empty) + text into a fresh file; what goes wrong, in the one-file path's words
+void write_csv_file(const std::string& path, const std::string& header, const char* text, uint64_t bytes)
+{
+    const int fd = open(path.c_str(), O_CREAT | O_TRUNC | O_WRONLY | O_CLOEXEC, 0666);
+    if (fd < 0) throw std::runtime_error("cannot open " + path);
+    auto put = [&](const char* p, uint64_t len) {
+        while (len) {
+            const ssize_t k = write(fd, p, (size_t)std::min<uint64_t>(len, (uint64_t)1 << 30));
+            if (k < 0 && errno == EINTR) continue;
+            if (k <= 0) return false;
+            p += k;
+            len -= (uint64_t)k;
+        }
+        return true;
+    };
+    const bool ok = put(header.data(), header.size()) && put(text, bytes);
+    if (close(fd) != 0 || !ok) throw std::runtime_error("writing " + path + " failed (disk full?)");
+}
+
+// the writers of one chunk: the chunk after the next may not be computed before they are through (the text buffer is theirs)
+struct WriteWave {
+    std::mutex mu;
+    std::condition_variable cv;
+    size_t left = 0;
+    void done()
+    {
+        {
+            std::lock_guard<std::mutex> lk(mu);
+            --left;
+        }
+        cv.notify_all();
+    }
+    void wait()
+    {
+        std::unique_lock<std::mutex> lk(mu);
+        cv.wait(lk, [this] { return left == 0; });
+    }
+};
+
+} // namespace
+
+std::vector<BatchResult> dist_exports_gpu(const std::vector<DistJob>& jobs, int device, BatchTotals* totals, EngineFuture* engine,
+                                          const std::function<void(size_t, const BatchResult&)>& done)
+{
+    const size_t n = jobs.size();
+    if (n == 0) {
+        BatchTotals none;
+        if (totals) *totals = none;
+        return {};
+    }
+    int n_threads = jobs[0].n_threads;
+    for (const auto& j : jobs) n_threads = std::min(n_threads, j.n_threads);
+    Driver d(n, n_threads, device, engine, done);
+    auto same_mode = [&](size_t a, size_t b) { return jobs[a].dist == jobs[b].dist && jobs[a].square == jobs[b].square && jobs[a].pid == jobs[b].pid; };
+    auto made = [&](size_t i, int route) {
+        BatchResult r;
+        r.ok = true;
+        r.route = route;
+        d.finish(i, std::move(r));
+    };
+
+    auto load_one = [&](size_t i, Loaded& f) {
+        const double t0 = now_s();
+        f.s = load_fasta(jobs[i].input, 1);
+        if (f.s.size() == 0) throw std::runtime_error("no sequences in " + jobs[i].input);
+        uint32_t longest = 0;
+        for (size_t r = 0; r < f.s.size(); ++r) longest = std::max(longest, f.s.length(r));
+        f.eligible = longest <= 65535; // all records count: no dedup, no tree heuristic
+        std::lock_guard<std::mutex> lk(d.tot_mu);
+        d.tot.load_s += now_s() - t0;
+    };
+
+    std::shared_ptr<WriteWave> waves[2]; // the writers of the last two chunks, by the text buffer they read
+    int n_calls = 0;
+    auto run_chunk = [&](const std::vector<size_t>& files) {
+        GpuLcsSource* src = d.the_engine();
         if (!src) {
-            fail_file(i, engine_error, 1);
-            continue;
+            for (size_t i : files) d.fail_file(i, d.engine_error, 0);
+            return;
         }
         try {
             const double t0 = now_s();
-            BatchResult r;
-            r.newick = guide_tree_newick_gpu(loaded[i]->s, *src, jobs[i].opt, nullptr);
-            r.ok = true;
-            r.route = 1;
-            {
-                std::lock_guard<std::mutex> lk(tot_mu);
-                tot.one_file_s += now_s() - t0;
-                ++tot.one_file;
+            const DistJob& mode = jobs[files[0]];
+            // the chunk's records, file after file as they were read: list k = the ids of file k, a contiguous range
+            size_t n_records = 0, n_codes = 0, n_name_bytes = 0;
+            for (size_t i : files) {
+                n_records += d.loaded[i]->s.size();
+                n_codes += d.loaded[i]->s.codes.size();
+                for (const auto& id : d.loaded[i]->s.ids) n_name_bytes += id.size();
             }
-            finish(i, std::move(r));
+            if (n_records > 0x7fffffffu) throw std::runtime_error("batch: a chunk of more than 2^31 records");
+            Bytes codes(n_codes);
+            std::vector<uint64_t> offsets, name_off;
+            offsets.reserve(n_records + 1);
+            name_off.reserve(n_records + 1);
+            std::string names;
+            names.reserve(n_name_bytes);
+            std::vector<int> ids(n_records);
+            std::vector<int64_t> list_off{0};
+            size_t code_at = 0;
+            for (size_t i : files) {
+                const SeqSet& s = d.loaded[i]->s;
+                std::copy(s.codes.begin(), s.codes.end(), codes.begin() + (ptrdiff_t)code_at);
+                for (size_t r = 0; r < s.size(); ++r) {
+                    offsets.push_back(s.offsets[r] + code_at);
+                    name_off.push_back(names.size());
+                    names.append(s.ids[r].c_str() + 1); // as the reference prints it: from the second character to the first NUL
+                }
+                code_at += s.codes.size();
+                list_off.push_back((int64_t)offsets.size());
+            }
+            offsets.push_back(code_at);
+            name_off.push_back(names.size());
+            for (size_t k = 0; k < n_records; ++k) ids[k] = (int)k;
+            src->upload(codes.data(), offsets); // input order, no sort, no dedup: the sets as they were read
+            const double t1 = now_s();
+            // the buffer this call's text comes in was the call before last's: its writers first
+            std::shared_ptr<WriteWave>& wave = waves[n_calls & 1];
+            if (wave) wave->wait();
+            const char* text = nullptr;
+            std::vector<uint64_t> text_off;
+            const double t_call = now_s(), kernel_ms0 = src->kernel_ms_total();
+            if (!src->dist_text_batch(names, name_off, ids.data(), list_off.data(), (int)files.size(), (int)mode.dist, mode.square, mode.pid, text,
+                                      text_off)) { // the text does not fit: file by file
+                d.one_file.insert(d.one_file.end(), files.begin(), files.end());
+                return;
+            }
+            ++n_calls;
+            const double t2 = now_s();
+            wave = std::make_shared<WriteWave>();
+            wave->left = files.size();
+            {
+                std::lock_guard<std::mutex> lk(d.tot_mu);
+                d.tot.upload_s += t1 - t0;
+                d.tot.device_s += t2 - t_call;
+                d.tot.kernel_s += 1e-3 * (src->kernel_ms_total() - kernel_ms0);
+                d.tot.text_bytes += text_off.back();
+                ++d.tot.chunks;
+            }
+            for (size_t k = 0; k < files.size(); ++k) {
+                const size_t i = files[k];
+                const char* const rows = text + text_off[k];
+                const uint64_t bytes = text_off[k + 1] - text_off[k];
+                std::shared_ptr<WriteWave> w = wave;
+                d.pool.submit([&, i, rows, bytes, w] {
+                    try {
+                        const double c0 = now_s();
+                        std::string header;
+                        if (jobs[i].square) { // as write_csv_text builds it
+                            for (const auto& id : d.loaded[i]->s.ids) {
+                                header += ',';
+                                header += id.c_str() + 1;
+                            }
+                            header += '\n';
+                        }
+                        write_csv_file(jobs[i].output, header, rows, bytes);
+                        {
+                            std::lock_guard<std::mutex> lk(d.tot_mu);
+                            d.tot.store_s += now_s() - c0;
+                            ++d.tot.in_chunks;
+                        }
+                        made(i, 0);
+                    } catch (const std::exception& e) {
+                        d.fail_file(i, e.what(), 0);
+                    }
+                    d.loaded[i].reset();
+                    w->done();
+                });
+            }
         } catch (const std::exception& e) {
-            fail_file(i, e.what(), 1);
+            for (size_t i : files) d.fail_file(i, e.what(), 0);
         }
-        loaded[i].reset();
-    }
-    pool.wait_idle();
-    if (g_abandon_engine_at_return && !profile_on()) (void)held.release();
-    if (totals) *totals = tot;
-    return results;
+    };
+
+    ChunkPacker packer{batch_value_budget(), batch_group_max()};
+    int mode_breaks = 0; // a change of (dist, square, pid) closes the chunk
+    size_t last_placed = n;
+    d.run(load_one,
+          [&](size_t i) {
+              const int64_t m = (int64_t)d.loaded[i]->s.size();
+              const int c = packer.place(m, jobs[i].square ? m * m : m * (m - 1) / 2, d.loaded[i]->eligible);
+              if (c < 0) return -1;
+              if (last_placed < n && !same_mode(last_placed, i)) ++mode_breaks;
+              last_placed = i;
+              return c + mode_breaks;
+          },
+          run_chunk,
+          [&](size_t i, GpuLcsSource& src) {
+              const double t0 = now_s();
+              const SeqSet& s = d.loaded[i]->s;
+              src.upload(s.codes.data(), s.offsets);
+              write_distance_csv(src, s.ids, jobs[i].dist, jobs[i].square, jobs[i].pid, jobs[i].output);
+              {
+                  std::lock_guard<std::mutex> lk(d.tot_mu);
+                  d.tot.one_file_s += now_s() - t0;
+                  ++d.tot.one_file;
+              }
+              made(i, 1);
+          });
+    if (totals) *totals = d.tot;
+    return std::move(d.results);
 }
 
 } // namespace famsa_host

@@ -21,7 +21,7 @@ using namespace famsa_host;
 
 namespace {
 thread_local std::string g_error;
-thread_local std::vector<std::string> g_batch_messages; // per file, of this thread's last famsa_host_trees_gpu
+thread_local std::vector<std::string> g_batch_messages; // per file, of this thread's last famsa_host_trees_gpu / _dist_exports_gpu
 
 // heuristic: 0 none, 1 parttree, 2 medoidtree; the int/float params override CParams::medoid when > 0
 TreeOptions make_options(const char* method, int distance, int keep_duplicates, int heuristic, int subtree_size,
@@ -212,6 +212,44 @@ int famsa_host_dist_export_gpu(const char* fasta, int device, int distance, int 
         SeqSet s = load_fasta(fasta);
         dist_export_gpu(s, device, (Distance)distance, square_matrix != 0, pid != 0, csv_path, nullptr);
         return 0;
+    } catch (const std::exception& e) {
+        return fail(e);
+    }
+}
+
+// -dist_export [-pid] [-square_matrix] of many FASTA files on ONE engine context (batch.h): csv_paths[i] receives what
+// famsa_host_dist_export_gpu writes for fastas[i].  status[i] = 0 (written) or -1 (failed: famsa_host_trees_message(i) says
+// why; the others are still made).  Returns the number of failed files, -1 on an error of the call itself.
+int famsa_host_dist_exports_gpu(const char* const* fastas, const char* const* csv_paths, int n_files, int device, int distance,
+                                int square_matrix, int pid, int* status)
+{
+    try {
+        if (n_files < 0 || (n_files > 0 && (!fastas || !csv_paths || !status))) throw std::runtime_error("famsa_host_dist_exports_gpu: bad argument");
+        if (distance != (int)Distance::indel_div_lcs && distance != (int)Distance::indel075_div_lcs)
+            throw std::runtime_error("famsa_host_dist_exports_gpu: unknown distance");
+        std::vector<DistJob> jobs((size_t)n_files);
+        const int threads = std::max(1, host_test_int("threads", default_host_threads()));
+        for (int i = 0; i < n_files; ++i) {
+            if (!fastas[i] || !csv_paths[i]) throw std::runtime_error("famsa_host_dist_exports_gpu: NULL path");
+            DistJob& j = jobs[(size_t)i];
+            j.input = fastas[i];
+            j.output = csv_paths[i];
+            j.dist = (Distance)distance;
+            j.square = square_matrix != 0;
+            j.pid = pid != 0;
+            j.n_threads = threads;
+        }
+        const std::vector<BatchResult> res = dist_exports_gpu(jobs, device);
+        g_batch_messages.assign((size_t)n_files, std::string());
+        int failed = 0;
+        for (int i = 0; i < n_files; ++i) {
+            status[i] = res[(size_t)i].ok ? 0 : -1;
+            if (!res[(size_t)i].ok) {
+                g_batch_messages[(size_t)i] = res[(size_t)i].message;
+                ++failed;
+            }
+        }
+        return failed;
     } catch (const std::exception& e) {
         return fail(e);
     }

@@ -2,10 +2,12 @@
 // Accepts the reference CLI's flags for this path (reference core/params.cpp:136-294, help text
 // :60-134):   famsa-gpu [options] <input.fasta> <output>
 //              famsa-gpu [tree options] -gt_export -batch <list>
-//   -batch <list>                            guide trees for many files in ONE process on one engine context: <list> is a
-//                                            text file of "input<TAB>output" lines (blank lines and lines starting with '#'
-//                                            are skipped); every output is what the one-file command writes for that input.
-//                                            Not with -dist_export, -stats, -dump_seeds, several GPUs or positional arguments
+//              famsa-gpu -dist_export [-pid] [-square_matrix] [-dist <measure>] -batch <list>
+//   -batch <list>                            guide trees, or distance matrices, for many files in ONE process on one engine
+//                                            context: <list> is a text file of "input<TAB>output" lines (blank lines and
+//                                            lines starting with '#' are skipped); every output is what the one-file command
+//                                            writes for that input.  With -gt_export or -dist_export, not both; not with
+//                                            -stats, -dump_seeds, several GPUs or positional arguments
 //   -gt <sl|slink|upgma|upgma_modified|nj|chained [seed]>   guide tree method (default sl)
 //   -gt_export                               write the guide tree in Newick format and stop
 //   -dist_export [-pid] [-square_matrix]     write the distance (or identity) matrix as CSV
@@ -62,6 +64,7 @@ void usage()
 {
     std::cerr << "Usage: famsa-gpu [options] <input_file> <output_file>\n"
                  "       famsa-gpu [tree options] -gt_export -batch <list_file>\n"
+                 "       famsa-gpu -dist_export [-pid] [-square_matrix] [-dist <measure>] -batch <list_file>\n"
                  "  -gt <sl | slink | upgma | upgma_modified | nj | chained [seed]>  guide tree method (default: sl)\n"
                  "  -gt_export            export the guide tree to the output file in Newick format\n"
                  "  -dist_export          export the distance matrix to the output file in CSV format\n"
@@ -76,8 +79,9 @@ void usage()
                  "  -stats <file>         the run's statistics as \"[stats]\" + key=value lines (what -v prints)\n"
                  "  -gpu <id[,id...]>     HIP device(s) (default 0); -gpus <n> = devices 0..n-1.  With several devices\n"
                  "                        the all-pairs work is tiled by row blocks over them\n"
-                 "  -batch <list_file>    with -gt_export: guide trees for many inputs in one process; the list holds one\n"
-                 "                        \"input<TAB>output\" per line ('#' starts a comment line).  -v prints the batch's totals\n"
+                 "  -batch <list_file>    with -gt_export or -dist_export: guide trees / distance matrices for many inputs in one\n"
+                 "                        process; the list holds one \"input<TAB>output\" per line ('#' starts a comment line).\n"
+                 "                        -v prints the batch's totals\n"
                  "  -t <n>, -v, -vv       accepted for compatibility / verbosity\n";
 }
 
@@ -178,13 +182,14 @@ int main(int argc, char** argv)
                 throw std::runtime_error(std::string(unsupported) + " is outside the scope of famsa-gpu (guide tree / distance stage only)");
         if (batch) {
             // refused before anything is started: what a batch does not cover
-            if (export_dist) throw std::runtime_error("-batch makes guide trees (-gt_export); it cannot be combined with -dist_export");
+            if (export_dist && export_tree)
+                throw std::runtime_error("-batch makes guide trees (-gt_export) or distance matrices (-dist_export) in one run, not both");
             if (!stats_path.empty()) throw std::runtime_error("-batch cannot be combined with -stats (-v prints the batch's totals)");
             if (!opt.dump_seeds_path.empty()) throw std::runtime_error("-batch cannot be combined with -dump_seeds (one seed file for many inputs)");
             if (devices.size() != 1) throw std::runtime_error("-batch runs on one GPU; it cannot be combined with -gpus / several -gpu ids");
             if (!params.empty())
                 throw std::runtime_error("-batch takes its inputs and outputs from the list file; unexpected argument: " + params[0]);
-            if (!export_tree) throw std::runtime_error("-batch needs -gt_export");
+            if (!export_tree && !export_dist) throw std::runtime_error("-batch needs -gt_export or -dist_export");
             const auto list = read_batch_list(batch_list);
             const auto clock_batch = std::chrono::steady_clock::now();
             {
@@ -195,7 +200,35 @@ int main(int argc, char** argv)
             int failed = 0;
             BatchTotals totals;
             double store_s = 0;
-            if (!list.empty()) {
+            if (export_dist) {
+                if (!list.empty()) {
+                    EngineFuture engine = start_engine(devices, 0);
+                    std::vector<DistJob> jobs(list.size());
+                    for (size_t i = 0; i < list.size(); ++i) {
+                        jobs[i].input = list[i].first;
+                        jobs[i].output = list[i].second;
+                        jobs[i].dist = opt.dist;
+                        jobs[i].square = square;
+                        jobs[i].pid = pid;
+                        jobs[i].n_threads = n_threads;
+                    }
+                    std::mutex mu; // stderr, the counter
+                    dist_exports_gpu(jobs, devices[0], &totals, &engine, [&](size_t i, const BatchResult& r) {
+                        if (r.ok) return;
+                        std::lock_guard<std::mutex> lk(mu);
+                        ++failed;
+                        std::cerr << "[ERROR] " << list[i].first << ": " << r.message << std::endl;
+                    });
+                }
+                if (verbose)
+                    std::cerr << "batch.files=" << list.size() << "\nbatch.chunks=" << totals.chunks << "\nbatch.files_in_chunks=" << totals.in_chunks
+                              << "\nbatch.files_one_file_route=" << totals.one_file << "\nbatch.files_failed=" << failed
+                              << "\nbatch.text_bytes=" << totals.text_bytes << "\nbatch.group_max=" << batch_group_max()
+                              << "\nbatch.value_budget=" << batch_value_budget() << "\ntime.load=" << totals.load_s << "\ntime.gpu_upload=" << totals.upload_s
+                              << "\ntime.device=" << totals.device_s << "\ntime.device_kernels=" << totals.kernel_s
+                              << "\ntime.one_file_route=" << totals.one_file_s << "\ntime.store=" << totals.store_s << "\ntime.main_until_exit="
+                              << std::chrono::duration<double>(std::chrono::steady_clock::now() - clock_batch).count() << "\n";
+            } else if (!list.empty()) {
                 EngineFuture engine = start_engine(devices, opt.heuristic != 0 ? fasttree_pool_threads(n_threads) : 0);
                 std::vector<BatchJob> jobs(list.size());
                 for (size_t i = 0; i < list.size(); ++i) {
@@ -225,7 +258,7 @@ int main(int argc, char** argv)
                     }
                 });
             }
-            if (verbose)
+            if (verbose && !export_dist)
                 std::cerr << "batch.files=" << list.size() << "\nbatch.chunks=" << totals.chunks << "\nbatch.files_in_chunks=" << totals.in_chunks
                           << "\nbatch.files_device_upgma=" << totals.device_upgma << "\nbatch.files_device_nj=" << totals.device_nj
                           << "\nbatch.files_one_file_route=" << totals.one_file << "\nbatch.files_failed=" << failed

@@ -265,6 +265,21 @@ void GpuLcsSource::text_end()
     text_slots_ = 0;
 }
 
+bool GpuLcsSource::dist_text_batch(const std::string& names, const std::vector<uint64_t>& name_off, const int* ids, const int64_t* offsets,
+                                   int n_groups, int distance_kind, bool square, bool pid, const char*& text, std::vector<uint64_t>& text_off)
+{
+    static_assert(sizeof(int) == sizeof(int32_t), "ids are int32");
+    text_off.assign((size_t)n_groups + 1, 0);
+    const int flags = (square ? LCSGPU_TEXT_SQUARE : 0) | (pid ? LCSGPU_TEXT_PID : 0);
+    const double t0 = now_s();
+    const int rc = lcsgpu_dist_text_batch(ctx_, names.data(), name_off.data(), ids, offsets, n_groups, distance_kind, flags, &text, text_off.data());
+    if (rc == LCSGPU_E_NOMEM) return false;
+    check(rc, "lcsgpu_dist_text_batch");
+    note(st_batch_, now_s() - t0, 0);
+    add_kernel_ms(ctx_);
+    return true;
+}
+
 void GpuLcsSource::triangle_ids(const int* ids, int n_ids, LcsBuf& out)
 {
     out.resize(n_ids > 1 ? (size_t)n_ids * (n_ids - 1) / 2 : 0, wide());

@@ -25,7 +25,8 @@ namespace famsa_host {
 // they were read instead of by length: measurements), leafmax=N (threads of that pool that may work on leaves while splits wait:
 // measurements), release_early / release_never / no_spare_tree / no_level_scratch (host memory of the tree heuristics as it was
 // before the second session of round 6: measurements), batch_pairs=N / batch_group_max=N (batch mode: the pair budget of a chunk and
-// the routing limit, batch.h -- tests force several chunks / the one-file route with them; unset, the defaults hold), batch_upgma_host
+// the routing limit, batch.h -- tests force several chunks / the one-file route with them; unset, the defaults hold), batch_values=N
+// (batch mode for matrices: the cap on a chunk's values below batch_pairs, batch.h: measurements), batch_upgma_host
 // (batch mode: the merges of -gt upgma / upgma_modified files in the host builders over the chunk's triangles, as before
 // lcsgpu_upgma_batch: tests, measurements), batch_nj_host (the same for -gt nj files and lcsgpu_nj_batch), matrix_whole_input (MatrixLcsSource below).  Not read on any product default path beyond that.
 bool host_test(const char* name);
@@ -153,6 +154,11 @@ public:
     // some merge no q was below FLT_MAX
     void nj_nodes_batch(const int* ids, const int64_t* offsets, int n_groups, int distance_kind, std::vector<int32_t>& left,
                         std::vector<int32_t>& right, std::vector<int32_t>& status);
+    // -dist_export rows of several id lists as text in one request (lcsgpu_dist_text_batch on the first device): names without
+    // '>' of all uploaded sequences; list g's rows at text[text_off[g] .. text_off[g + 1]), valid until the second following
+    // request.  false: the text does not fit the device or the pinned host memory (nothing was made); other errors throw
+    bool dist_text_batch(const std::string& names, const std::vector<uint64_t>& name_off, const int* ids, const int64_t* offsets, int n_groups,
+                         int distance_kind, bool square, bool pid, const char*& text, std::vector<uint64_t>& text_off);
     // per uploaded sequence: 1 if it is orientation sensitive as a ref (lcsgpu_orientation_flags)
     const std::vector<uint8_t>& orientation_flags() const { return flags_; }
     bool upgma_nodes(int distance_kind, bool modified, std::vector<int32_t>& left, std::vector<int32_t>& right) override;

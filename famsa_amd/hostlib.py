@@ -36,6 +36,7 @@ class Host:
                                              C.c_void_p, C.c_void_p]
         lib.famsa_host_trees_message.restype = C.c_char_p
         lib.famsa_host_trees_message.argtypes = [C.c_int]
+        lib.famsa_host_dist_exports_gpu.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         lib.famsa_host_batch_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p]
         lib.famsa_host_dist_export_gpu.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p]
         lib.famsa_host_workset.argtypes = [C.c_char_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
@@ -124,6 +125,21 @@ class Host:
         if self.lib.famsa_host_dist_export_gpu(fasta.encode(), device, DIST[distance], int(square_matrix), int(pid),
                                                path.encode()) != 0:
             raise self._err()
+
+    def dist_exports_gpu(self, fastas, paths, distance="indel075_div_lcs", square_matrix=False, pid=False, device=0):
+        """Distance files of many inputs on one engine context: a list with None for a file made or, where the file
+        failed, a RuntimeError with its message."""
+        n = len(fastas)
+        if len(paths) != n:
+            raise ValueError("one output path per input")
+        ins = (C.c_char_p * max(n, 1))(*[f.encode() for f in fastas])
+        outs = (C.c_char_p * max(n, 1))(*[f.encode() for f in paths])
+        status = np.zeros(max(n, 1), np.int32)
+        if self.lib.famsa_host_dist_exports_gpu(C.cast(ins, C.c_void_p), C.cast(outs, C.c_void_p), n, device, DIST[distance],
+                                                int(square_matrix), int(pid), status.ctypes.data) < 0:
+            raise self._err()
+        return [None if status[i] == 0 else RuntimeError(self.lib.famsa_host_trees_message(i).decode(errors="replace"))
+                for i in range(n)]
 
     def workset(self, fasta, n, keep_duplicates=False):
         a = np.zeros(n, np.int32)
@@ -214,3 +230,19 @@ def guide_trees(fastas, gt="sl", distance="indel075_div_lcs", keep_duplicates=Fa
 def dist_export(fasta, csv_path, distance="indel075_div_lcs", square_matrix=False, pid=False, device=0):
     """`famsa -dist_export [-square_matrix] [-pid] <fasta> <csv_path>` with the LCS on GPU `device`."""
     _host().dist_export_gpu(fasta, csv_path, distance, square_matrix, pid, device)
+
+
+def dist_exports(fastas, csv_paths, distance="indel075_div_lcs", square_matrix=False, pid=False, device=0, on_error="raise"):
+    """dist_export for many files in ONE process on ONE engine context: csv_paths[i] receives what dist_export writes for
+    fastas[i] alone.  Files up to the routing limit are made together, chunk by chunk (one upload and one formatter launch
+    sequence per chunk, the files written by worker threads meanwhile); the rest goes through the one-file path on the same
+    context.  Returns a list with None per file made.  A file that fails does not stop the others: on_error="raise" raises
+    the first failure after all files are done, on_error="return" puts the exception into that file's slot."""
+    if on_error not in ("raise", "return"):
+        raise ValueError("on_error must be 'raise' or 'return'")
+    out = _host().dist_exports_gpu([os.fspath(f) for f in fastas], [os.fspath(f) for f in csv_paths], distance, square_matrix, pid, device)
+    if on_error == "raise":
+        for r in out:
+            if isinstance(r, Exception):
+                raise r
+    return out

@@ -84,6 +84,7 @@ def load_library():
         "lcsgpu_dist_text_submit": (C.c_int, [vp, i32, i32, i32]),
         "lcsgpu_dist_text_wait": (C.c_int, [vp, i32, C.POINTER(vp), C.POINTER(C.c_uint64)]),
         "lcsgpu_dist_text_end": (C.c_int, [vp]),
+        "lcsgpu_dist_text_batch": (C.c_int, [vp, C.c_char_p, vp, vp, vp, i32, C.c_int, C.c_int, C.POINTER(vp), vp]),
         "lcsgpu_sync": (C.c_int, [vp]),
         "lcsgpu_last_kernel_ms": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(i32)]),
         "lcsgpu_total_kernel_ms": (C.c_int, [vp, C.POINTER(C.c_double)]),
@@ -103,6 +104,7 @@ MST_TRIANGLE_ORIENTATION = 0x100
 MST_BATCH_MAX_MEMBERS = 4096  # lcsgpu_mst_prim_batch: members of one group at most
 UPGMA_BATCH_MAX_MEMBERS = 4096  # lcsgpu_upgma_batch: members of one group at most
 NJ_BATCH_MAX_MEMBERS = 2048  # lcsgpu_nj_batch: members of one group at most
+DIST_TEXT_BATCH_MAX_MEMBERS = 4096  # lcsgpu_dist_text_batch: members of one list at most
 MST_COMPUTE = 0x200  # lcsgpu_mst_shard_begin: the LCS launch itself does the local half (see include/lcsgpu.h)
 
 
@@ -456,6 +458,30 @@ class LcsGpu:
         finally:
             self._lib.lcsgpu_dist_text_end(self._ctx)
         return b"".join(out)
+
+    def dist_text_batch(self, names, groups, kind=1, square=False, pid=False, copy=True):
+        """-dist_export rows of several id lists of the uploaded set, one call (lcsgpu_dist_text_batch): `names` without
+        '>' of ALL uploaded sequences; returns a list with the bytes of every list's rows.  copy=False: memoryviews of the
+        context's pinned buffer instead, valid until the second following call."""
+        raw = [x.encode("latin-1") if isinstance(x, str) else bytes(x) for x in names]
+        off = np.zeros(len(raw) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(x) for x in raw], dtype=np.uint64)
+        sizes = [len(g) for g in groups]
+        offs = np.zeros(len(groups) + 1, dtype=np.int64)
+        np.cumsum(sizes, out=offs[1:])
+        ids = np.ascontiguousarray(np.concatenate([np.asarray(g, np.int32) for g in groups]) if offs[-1] else np.zeros(0, np.int32),
+                                   dtype=np.int32)
+        flags = (1 if square else 0) | (2 if pid else 0)
+        ptr = C.c_void_p(0)
+        text_off = np.zeros(len(groups) + 1, dtype=np.uint64)
+        self._check(self._lib.lcsgpu_dist_text_batch(self._ctx, b"".join(raw), off.ctypes.data, ids.ctypes.data, offs.ctypes.data, len(groups),
+                                                     int(kind), flags, C.byref(ptr), text_off.ctypes.data))
+        total = int(text_off[-1])
+        if not copy:
+            whole = memoryview((C.c_char * total).from_address(ptr.value)).cast("B") if total else memoryview(b"")
+            return [whole[int(text_off[g]):int(text_off[g + 1])] for g in range(len(groups))]
+        whole = C.string_at(ptr.value, total) if total else b""
+        return [whole[int(text_off[g]):int(text_off[g + 1])] for g in range(len(groups))]
 
     def sync(self):
         self._check(self._lib.lcsgpu_sync(self._ctx))

@@ -474,6 +474,32 @@ int lcsgpu_dist_text_submit(lcsgpu_ctx* ctx, int32_t slot, int32_t row_begin, in
 int lcsgpu_dist_text_wait(lcsgpu_ctx* ctx, int32_t slot, const char** text, uint64_t* n_bytes);
 int lcsgpu_dist_text_end(lcsgpu_ctx* ctx);
 
+/* -dist_export for MANY id lists of the uploaded set in one call (a directory of small families: one process, one upload,
+ * one call per chunk of files).  names / name_offsets (HOST; copied): the names, without '>', of ALL uploaded sequences,
+ * indexed by uploaded id.  List g = ids[group_offsets[g] .. group_offsets[g+1]): any ids of the set in any order, an id
+ * may appear in several lists.  text[text_offsets[g] .. text_offsets[g+1]) holds the rows of list g one after the other:
+ * exactly the bytes lcsgpu_dist_text_* delivers for that list uploaded alone in list order -- row k = "<name>," + the values
+ * against the members c < k (all m members with LCSGPU_TEXT_SQUARE), the last separator a newline; a list of one member
+ * gives "name" + newline in the lower form, an empty list no byte.  The header line of -square_matrix is the caller's.
+ * Lower form: the lists' packed triangles as lcsgpu_lcs_triangles_batch computes them (ref = the later member = the row:
+ * calculateDistanceVector's orientation, so orientation-sensitive sequences are served like any other).  Square form:
+ * every list's m x m rectangle with every member as the ref of its own row, the diagonal included -- nothing is mirrored.
+ * The values never leave the device as numbers: one launch sequence formats all rows of all lists (lengths, scans, write).
+ * Device text memory is sized exactly (the lists' offsets and the total come to the host in the middle of the call), so
+ * LCSGPU_E_NOMEM -- nothing written -- means the text itself does not fit.
+ * *text is pinned host memory owned by the context.  Two buffers alternate: a call's text stays valid until the SECOND
+ * following call of this function on the context (or lcsgpu_destroy), so a caller can drain chunk k while chunk k + 1 is
+ * computed.  text_offsets: HOST, n_groups + 1 entries.  ONE host thread drives this call on a context.
+ * distance_kind / flags as for lcsgpu_dist_text_begin.
+ * Refused with nothing computed and the outputs untouched: LCSGPU_E_UNSUPPORTED for a list of more than
+ * LCSGPU_DIST_TEXT_BATCH_MAX_MEMBERS members or a named sequence longer than 65535 residues (16-bit LCS values);
+ * LCSGPU_E_INVALID for an id out of range, NULL arguments, descending offsets.
+ * Replaces: DistanceCalculator::run, once per list (tree/DistanceCalculator.cpp:10-120). */
+#define LCSGPU_DIST_TEXT_BATCH_MAX_MEMBERS 4096
+int lcsgpu_dist_text_batch(lcsgpu_ctx* ctx, const char* names, const uint64_t* name_offsets, const int32_t* ids,
+                           const int64_t* group_offsets, int32_t n_groups, int distance_kind, int flags,
+                           const char** text, uint64_t* text_offsets);
+
 /* ---- The FastTree recursion level by level: all splits of a level in one call ------------------------------------
  * lcsgpu_clarans_batch: lcsgpu_clarans for n_jobs samples at once -- sample g = ids[offsets[g] .. offsets[g+1]) with
  *   n_medoids[g] medoids (slots < n_fixed pinned); medoids_out receives the samples' medoids one after the other.  One

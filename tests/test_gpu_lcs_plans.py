@@ -276,7 +276,7 @@ def test_triangle_at_the_full_complement(engine, oracle, trace, cls):
 # ---- 3. fused launches at their own full complement ----------------------------------------------------------------------------
 
 # every distinct head of the fused table with every register group it occurs with
-FUSED = [("pipe", h) for h in (4, 8, 10, 12, 13, 16, 17, 20, 24, 32, 34, 44, 52, 58, 64)]
+FUSED = [("pipe", h) for h in (4, 8, 10, 12, 13, 16, 17, 20, 24, 32, 34, 44, 52, 58, 64)] + [("quirk", h) for h in QUIRK_H]
 BOTH_KINDS = [("pipe", 13), ("pipe", 20), ("pipe", 44)]
 
 
@@ -299,8 +299,8 @@ def _same_edges(a, b):
 @pytest.mark.parametrize("cls", FUSED, ids=_id)
 def test_fused_launches_at_their_full_complement(engine, oracle, trace, monkeypatch, cls):
     """mst_prim with the fold in the LCS launch -- every round (recompute) or round 0 (fused) -- on a duplicate-heavy set
-    (pool repeats: the records' id order decides) against Prim over the gathered oracle square (a quirk class would run in
-    the triangle's orientation; none is in the list yet)."""
+    (pool repeats: the records' id order decides) against Prim over the gathered oracle square (the quirk classes run in
+    the triangle's orientation, ref = the larger id)."""
     pool = _pool(oracle, cls)
     full = FUSED_FULL[cls[0]][cls[1]]
     orientation = MST_TRIANGLE_ORIENTATION if cls[0] == "quirk" else 0
